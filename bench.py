@@ -49,6 +49,28 @@ PRECISION_DTYPE = {
     "fp32": "fp32 (every nn.Linear product as bf16x6 on the bf16 MFMA = fp32-accurate; attention core on the f32 MFMA)"}
 VIT_B = dict(decoder="classification", image_size=224, patch_size=16, num_classes=1000, dim=768, depth=12, heads=12,
              mlp_dim=3072, dropout=0.0, emb_dropout=0.0)
+DUMP_MAX_ELEMS = 1 << 21            # --dump-outputs: a larger array is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs DIR``: each array as DIR/<name>.npy in float32, its shape kept.  An array of more than DUMP_MAX_ELEMS elements
+    is written flat as DIR/<name>_sample.npy: the elements at DUMP_MAX_ELEMS indices drawn with a fixed seed and sorted, the same
+    indices for any array of the same size -- so two builds' files compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(20240601)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def _lib_digest16():
@@ -282,7 +304,13 @@ def main():
                     help="no compute: only the multi-process launch, rendezvous, barriers and the JSON line (CPU test)")
     ap.add_argument("--dry-run-fail-rank", type=int, default=None,
                     help="--dry-run only: this rank exits non-zero before the rendezvous (the launcher must fail, not hang)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step returned (loss, logits; seg: accuracy, "
+                         "prediction) and the weights and gradients it left as DIR/<name>.npy in float32, at most 64 MB "
+                         "(see dump_outputs); the inputs are seeded, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.batch is None:
         args.batch = 1024 if args.workload == "infer-int8" else 256
@@ -350,6 +378,18 @@ def main():
     else:
         labels = torch.randint(0, 1000, (args.batch,), generator=g).to(dev)
     vit.train()
+    last = {}                                                # --dump-outputs: what the latest step handed its caller
+
+    def keep(name, t):
+        if args.dump_outputs:
+            last[name] = t
+        return t
+
+    def seg_loss(m, x, y):
+        loss, acc, pred = m.segmentation_loss(x, y)             # what segmentation/train.py runs here (engine.py)
+        keep("accuracy", acc)
+        keep("prediction", pred)
+        return loss
 
     if args.workload == "infer-int8":
         vit.eval()
@@ -360,14 +400,14 @@ def main():
 
         def step():
             with torch.no_grad():
-                return vit(img).float().mean()
+                return keep("logits", vit(img)).float().mean()
     else:
         def step():
             opt.zero_grad()
             if args.workload in ("seg", "seg256") and not args.seg_unfused:
-                loss = vit.segmentation_loss(img, labels)[0]     # what segmentation/train.py runs here (engine.py)
+                loss = seg_loss(vit, img, labels)
             else:
-                loss = cross_entropy(vit(img), labels)
+                loss = cross_entropy(keep("logits", vit(img)), labels)
             loss.backward()
             reducer.finish()
             if not args.no_optimizer:
@@ -379,7 +419,8 @@ def main():
             raise SystemExit("--graph: single-GPU training workloads with the optimizer step")
         from myrtle_vision.utils.graph import GraphedTrainStep
         seg_fused = args.workload in ("seg", "seg256") and not args.seg_unfused
-        loss_fn = (lambda m, x, y: m.segmentation_loss(x, y)[0]) if seg_fused else (lambda m, x, y: cross_entropy(m(x), y))
+        # under capture, keep() holds the graph's static outputs: each replay rewrites them in place
+        loss_fn = seg_loss if seg_fused else (lambda m, x, y: cross_entropy(keep("logits", m(x)), y))
         graphed = GraphedTrainStep(vit, opt, loss_fn, img, labels)
 
         def step():                                          # noqa: F811  (replaces the eager step)
@@ -405,6 +446,11 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ops.set_kernel_timer(None)
+    if args.dump_outputs and rank == 0:
+        outputs = {"logits_mean" if args.workload == "infer-int8" else "loss": loss, **last}
+        if args.workload != "infer-int8":
+            outputs.update(params=arena.flat_param, grads=arena.flat_grad)      # the weights and gradients the last step left
+        dump_outputs(args.dump_outputs, outputs)
     final_loss = float(loss.detach())
     exposed_ms = reducer.exposed_ms()                           # per rank; the slowest rank's is reported
     if world > 1:

@@ -577,6 +577,32 @@ def test_bench_eight_ranks_dry_run_and_a_dying_rank_fails_the_command():
     assert time.time() - t0 < 300
 
 
+def test_bench_dump_outputs_writes_float32_within_budget_and_samples_by_a_fixed_seed(tmp_path):
+    """``bench.py --dump-outputs DIR``: every array as float32 .npy, shape kept; a large one as a seeded sample that is the same
+    from run to run (two builds compare element for element); 64 MB in all at most.  ``--steps`` below 1 is refused."""
+    import subprocess
+    import sys
+    import bench
+    big = torch.arange(3 * bench.DUMP_MAX_ELEMS, dtype=torch.float32)
+    logits = torch.randn(8, 10).bfloat16()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": torch.tensor(2.5), "logits": logits, "params": big})
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["logits.npy", "loss.npy", "params_sample.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss.npy"].shape == () and float(a["loss.npy"]) == 2.5
+    assert np.array_equal(a["logits.npy"], logits.float().numpy())
+    s = a["params_sample.npy"]
+    assert s.shape == (bench.DUMP_MAX_ELEMS,) and (np.diff(s) >= 0).all() and s.max() > 2 * bench.DUMP_MAX_ELEMS
+    assert np.array_equal(s, np.load(tmp_path / "b" / "params_sample.npy"))
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big for i in range(bench.DUMP_MAX_BYTES // (4 * bench.DUMP_MAX_ELEMS) + 1)})
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 @pytest.mark.parametrize("fmt,outputs", [("FP16_32", False), ("TF32", False), ("FP16_16", True)])
 def test_prepared_modules_actually_hold_their_quantisers(fmt, outputs):
     """Regression (round 2): quantisers assigned to a class-swapped module live in nn.Module._modules, which a class-level
