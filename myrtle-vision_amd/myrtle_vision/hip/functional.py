@@ -460,18 +460,23 @@ def patch_embed(img, weight, bias, cls_token, pos, patch, prec):
 # gradient dx can also emit (a) dx in bf16 and (b) its column sums -- exactly what the NEXT block function to run
 # (the one whose output gradient is this dx) needs as MFMA operand and as output-projection bias gradient.  Keeping
 # a strong reference to dx pins its address, so a pointer match identifies the tensor unambiguously.
+# Each entry carries its KIND: "bf16" (dx16, the [rows, dim] bf16 copy of dx) or ("split", nseg) (the [rows, nseg * dim] bf16
+# pieces of dx).  Precision is per block, so producer and consumer may run different arithmetics: a consumer takes only the kind
+# it reads (a bf16 block in front of an fp32 one must not read the latter's pieces as its dY) and otherwise computes its own.
 _side = {}
 
 
-def _publish_side(dx, dx16, colsum):
+def _publish_side(dx, side, colsum, kind):
     _side.clear()
-    _side[dx.data_ptr()] = (dx, dx16, colsum)
+    _side[dx.data_ptr()] = (dx, side, colsum, kind)
 
 
-def _take_side(dout, rows, dim):
+def _take_side(dout, rows, dim, kind):
+    """(side tensor, column sums) published for ``dout`` if it is of ``kind`` ("bf16" or ("split", nseg)), else (None, None)."""
     ent = _side.pop(dout.data_ptr(), None)
     _side.clear()
-    if ent is None or ent[0].shape != dout.shape or ent[1].shape[0] != rows or ent[1].shape[1] not in (dim, ops.current_segments() * dim):
+    width = dim if kind == "bf16" else kind[1] * dim
+    if ent is None or ent[3] != kind or ent[0].shape != dout.shape or tuple(ent[1].shape) != (rows, width):
         return None, None
     return ent[1], ent[2]
 
@@ -485,14 +490,14 @@ def _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, adt, up_bias=None):
         dx16 = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
         cs = ops.grad_out(up_bias, (D,), x.device)
         dg, db = ops.layernorm_bwd(dy, x, D, g, mean, rstd, dout, dx, D, M, D, dx16=dx16, dx_colsum=cs, beta=b)
-        _publish_side(dx, dx16, cs)
+        _publish_side(dx, dx16, cs, "bf16")
     elif D <= 1024 and ops.x6_block_ok(M, D):
         # split-operand modes: dx also leaves as the pieces the consumer's dW / dX products read, with its column sums (that Linear's
         # bias gradient): the consumer (the block before this one, _take_side) then needs no split pass over dx
         dx6 = ops._split_buffer(M, D, x.device)
         cs = ops.grad_out(up_bias, (D,), x.device)
         dg, db = ops.layernorm_bwd(dy, x, D, g, mean, rstd, dout, dx, D, M, D, dx_split=dx6, dx_colsum=cs, beta=b)
-        _publish_side(dx, dx6, cs)
+        _publish_side(dx, dx6, cs, ("split", ops.current_segments()))
     else:
         dg, db = ops.layernorm_bwd(dy, x, D, g, mean, rstd, dout, dx, D, M, D, beta=b)
     return dx, dg, db
@@ -610,7 +615,7 @@ class _AttnBlock(Function):
             y6, o6, probs = y, o, lse_or_probs
             dout = _c(dout)
             b, bqkv, bo = ctx.small
-            d6, dbo = _take_side(dout, M, D)                                  # the producing LayerNorm backward left both
+            d6, dbo = _take_side(dout, M, D, ("split", ops.current_segments()))   # the producing LayerNorm backward left both
             if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
                 dbo = ops.grad_out(bo, (D,), x.device)
                 d6 = ops.split_ex(dout.view(M, D), M, D, colsum_out=dbo)      # one pass: the split and the bias gradient
@@ -636,7 +641,7 @@ class _AttnBlock(Function):
             return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None
         adt = y.dtype
         dout = _c(dout)
-        d_act, dbo = _take_side(dout, M, D) if adt == torch.bfloat16 else (None, None)
+        d_act, dbo = _take_side(dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
         if d_act is None:
             d_act = ops.cast(dout, adt).view(M, D)                # dY of the projection, activation dtype
         b, bqkv, bo = ctx.small
@@ -725,7 +730,7 @@ class _MlpBlock(Function):
             y6, a6 = y, a
             dout = _c(dout)
             b, b1, b2 = ctx.small
-            d6, db2 = _take_side(dout, M, D)
+            d6, db2 = _take_side(dout, M, D, ("split", ops.current_segments()))
             if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
                 db2 = ops.grad_out(b2, (D,), x.device)
                 d6 = ops.split_ex(dout.view(M, D), M, D, colsum_out=db2)
@@ -744,7 +749,7 @@ class _MlpBlock(Function):
             return dx, dg, db, dw1, db1, dw2, db2, None
         adt = y.dtype
         dout = _c(dout)
-        d_act, db2 = _take_side(dout, M, D) if adt == torch.bfloat16 else (None, None)
+        d_act, db2 = _take_side(dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
         if d_act is None:
             d_act = ops.cast(dout, adt).view(M, D)
         b, b1, b2 = ctx.small

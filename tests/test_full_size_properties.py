@@ -34,6 +34,11 @@ def rel_l2(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
+def max_rel(a, b):
+    """max |a - b| / max |b| (b in fp64)."""
+    return float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-30))
+
+
 # ---------------------------------------------------------------- full-size kernels, sampled rows vs fp64
 @pytest.mark.parametrize("N,K", [(2304, 768), (768, 3072), (3072, 768)])
 def test_full_size_gemm_nt_sampled_rows(ops, N, K):
@@ -115,6 +120,64 @@ def test_full_size_layernorm_rows_are_normalised(ops):
     y, mean, rstd = ops.layernorm_fwd(x, D, M, D, gamma, beta, torch.float32)
     assert float(y.mean(1).abs().max()) < 1e-5 and float((y.var(1, unbiased=False) - 1).abs().max()) < 1e-4
     assert rel_l2(mean, x.double().mean(1)) < 1e-6
+
+
+@pytest.mark.parametrize("M", [M_FULL, 255 * 197])                # 255 images: 50 235 rows, 5 pad rows up to the next 32
+@pytest.mark.parametrize("form", ["bf16", "split3"])
+def test_full_size_layernorm_bwd_fused_outputs(ops, M, form):
+    """LayerNorm backward at D = 768 in the forms the training step runs at full size: the bf16 step's (bf16 dy, dx_add, dx16,
+    dx_colsum) and the tolerance-meeting line's (bf16x3h: fp32 dy, dx_add, the three bf16 pieces of dx, dx_colsum).  Every wave of
+    the capped grid accumulates its column partials over ~16 rows here.  Sampled rows of dx and the full dgamma / dbeta /
+    column sums against fp64 on the GPU, and the bitwise identities with the plain and the colsum-only forms."""
+    from oracle.vit_oracle import layer_norm as ln_oracle
+    D = 768
+    cg = torch.Generator(device="cuda")
+    x = torch.randn(M, D, device="cuda", generator=cg.manual_seed(30)) * 2 + 0.5
+    gam = torch.randn(D, device="cuda", generator=cg.manual_seed(31)) * 0.1 + 1
+    bet = torch.randn(D, device="cuda", generator=cg.manual_seed(32)) * 0.1
+    dy = torch.randn(M, D, device="cuda", generator=cg.manual_seed(33)).to(torch.bfloat16 if form == "bf16" else torch.float32)
+    add = torch.randn(M, D, device="cuda", generator=cg.manual_seed(34))
+    _, mean, rstd = ops.layernorm_fwd(x, D, M, D, gam, bet, torch.float32)
+
+    def bwd(**kw):
+        dx = torch.full((M, D), float("nan"), device="cuda")
+        dg, db = ops.layernorm_bwd(dy, x, D, gam, mean, rstd, add, dx, D, M, D, **kw)
+        return dx, dg.clone(), db.clone()
+
+    dx, dg, db = bwd()
+    cs_only = torch.full((D,), float("nan"), device="cuda")
+    fused = bwd(dx_colsum=cs_only)
+    assert all(torch.equal(a, b) for a, b in zip(fused, (dx, dg, db)))
+    cs = torch.full((D,), float("nan"), device="cuda")
+    if form == "bf16":
+        dx16 = torch.empty(M, D, dtype=torch.bfloat16, device="cuda")
+        fused = bwd(dx16=dx16, dx_colsum=cs)
+        assert torch.equal(dx16.view(torch.int16), dx.to(torch.bfloat16).view(torch.int16))
+    else:
+        with ops.segments(3):
+            full = torch.empty(ops.pad32(M), 3 * D, dtype=torch.bfloat16, device="cuda")
+            full[:M].fill_(float("nan"))
+            full[M:].zero_()
+            fused = bwd(dx_split=full[:M], dx_colsum=cs)
+            assert torch.equal(full[:M].view(torch.int16), ops.split_ex(dx, M, D).view(torch.int16))
+        assert not bool(full[M:].any())
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(fused, (dx, dg, db)))
+    assert torch.equal(cs.view(torch.int32), cs_only.view(torch.int32))
+
+    xr = x.double().requires_grad_(True)
+    gr, br = gam.double().requires_grad_(True), bet.double().requires_grad_(True)
+    ln_oracle(xr, gr, br).backward(dy.double())
+    dx_ref = xr.grad + add.double()
+    rows = torch.cat([torch.arange(0, 300), torch.randint(0, M, (2048,), generator=g(35)), torch.arange(M - 300, M)]).cuda()
+
+    # per-row arithmetic, as in tests/test_layernorm_backward.py (5e-6);  fp32 column sums over 50 k rows (a wave's ~16 rows, the
+    # 4-wave tree, then the finishing reduce over the capped grid's partial rows): measured dx 1.1e-7, dgamma 2.7e-7, dbeta 2.5e-7,
+    # column sums 2.2e-7 against fp64 sums of the kernel's dx and 2.3e-7 against the reference's
+    assert max_rel(dx[rows], dx_ref[rows]) < 5e-6
+    assert max_rel(dg, gr.grad) < 5e-6
+    assert max_rel(db, br.grad) < 5e-6
+    assert max_rel(cs, dx.double().sum(0)) < 2e-6
+    assert max_rel(cs, dx_ref.sum(0)) < 5e-6
 
 
 # ---------------------------------------------------------------- the whole model at batch 256

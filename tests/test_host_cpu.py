@@ -360,6 +360,43 @@ def test_segment_scope_is_per_thread_and_follows_the_precision():
     assert not ViT(decoder="segmentation", prune_dead_tokens=True, **kw).transformer.cls_only_tail
 
 
+def test_block_side_channel_hands_over_only_the_kind_the_consumer_reads():
+    """The LayerNorm backward of one fused block publishes dx's bf16 copy ("bf16", [M, D]) or its split pieces (("split", nseg),
+    [M, nseg * D]) for the block before it.  Precision is per block, so every producer / consumer pair can meet: a consumer takes
+    only its own kind -- a bf16 block must never read an fp32 block's [M, 6D] pieces as its [M, D] dY -- and anything else hands
+    back (None, None), so the consumer computes its own dY."""
+    from myrtle_vision.hip import functional as F
+
+    def _taken_nothing(got):
+        return got[0] is None and got[1] is None
+
+    M, D = 8, 4
+    kinds = ["bf16", ("split", 3), ("split", 6)]
+    for prod in kinds:
+        for cons in kinds:
+            dx = torch.zeros(M, D)
+            side = torch.zeros(M, D if prod == "bf16" else prod[1] * D, dtype=torch.bfloat16)
+            cs = torch.zeros(D)
+            F._publish_side(dx, side, cs, prod)
+            got = F._take_side(dx, M, D, cons)
+            if prod == cons:
+                assert got[0] is side and got[1] is cs, (prod, cons)
+            else:
+                assert got[0] is None and got[1] is None, (prod, cons)
+            assert _taken_nothing(F._take_side(dx, M, D, prod))          # one-shot: the slot is empty after any take
+    dx = torch.zeros(M, D)
+    side = torch.zeros(M, 6 * D, dtype=torch.bfloat16)
+    F._publish_side(dx, side, None, ("split", 6))
+    assert _taken_nothing(F._take_side(dx, M, D, "bf16"))               # the [8, 24] pieces are not an [8, 4] dY
+    # a different tensor, another row count, or a side tensor of the wrong width for its tag is not taken either
+    F._publish_side(dx, torch.zeros(M, D, dtype=torch.bfloat16), None, "bf16")
+    assert _taken_nothing(F._take_side(torch.zeros(M, D), M, D, "bf16"))
+    F._publish_side(dx, torch.zeros(M, D, dtype=torch.bfloat16), None, "bf16")
+    assert _taken_nothing(F._take_side(dx, M - 1, D, "bf16"))
+    F._publish_side(dx, torch.zeros(M, 3 * D, dtype=torch.bfloat16), None, ("split", 6))
+    assert _taken_nothing(F._take_side(dx, M, D, ("split", 6)))
+
+
 def test_get_models_reads_reference_config_schema(tmp_path):
     from myrtle_vision.utils.models import get_models
     cfg = json.load(open(os.path.join(ROOT, "classification", "train_configs", "vit_tiny.json")))
