@@ -155,6 +155,16 @@ int mv_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int H
  * so no separate pass over dqkv is needed for it. */
 int mv_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* colsum,
                      int B, int N, int H, float scale, mv_stream_t stream);
+/* The same attention core for any 1 <= N <= 8192 (Attention.forward vit.py:87-96; the position table interpolated to larger
+ * grids, vit.py:216-218,292-302, gives 577 tokens at 384^2, 1 025 at 512^2): key-tiled kernels that stream K / V (or Q / dO)
+ * through LDS in 64-row blocks with an online softmax, so no [N, N] tensor exists.  Layouts, alignment (16 bytes for every
+ * bf16 tensor), lse and colsum as mv_attention_fwd / mv_attention_bwd; the same rounding points (P and dS rounded to bf16 before
+ * their products, fp32 accumulation, outputs rounded once).  Backward: delta_ws is a caller-provided fp32 workspace of
+ * B * H * N floats (it receives rowsum(dout * out)); colsum here sums the bf16 dqkv rows in a fixed order.  Deterministic: no
+ * atomics, every output has one owner.  ops.attention_fwd / _bwd take these for N > 320 and the kernels above otherwise. */
+int mv_attention_fwd_long(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, mv_stream_t stream);
+int mv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, float* delta_ws, void* dqkv,
+                          float* colsum, int B, int N, int H, float scale, mv_stream_t stream);
 /* The attention core of precision "bf16x3" (vit.py:87-96 between fp32 tensors): the fused kernels above on IEEE-half operands with
  * fp32 accumulation, softmax and OUTPUTS; N <= 288 (N <= 208: the 13-key-tile kernels; above: the two-pass kernels of the 257-token case).  qkv16: half [B, N, 3, H, 64] (mv_cast to MV_F16 of the fp32 to_qkv output);
  * out / lse as mv_attention_fwd but out is fp32.  Backward: mv_attention_bwd_prep_f16 turns the fp32 dout [B, N, H*64] into half

@@ -818,12 +818,21 @@ def colsum(x, rows, cols, ld, out):
 # ------------------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------------------
+ATTN_SHORT_MAX_N = 320      # the whole-head kernels (mv_attention_fwd / _bwd): K and V of a head in LDS
+ATTN_LONG_MAX_N = 8192      # the key-tiled kernels (mv_attention_fwd_long / _bwd_long)
+# A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320 back to the materialised fp32 path
+ATTN_LONG = True
+
+
 def attention_fused_supported(qkv_dtype, N, dim_head):
-    return qkv_dtype == torch.bfloat16 and dim_head == 64 and N <= 320
+    cap = ATTN_LONG_MAX_N if ATTN_LONG else ATTN_SHORT_MAX_N
+    return qkv_dtype == torch.bfloat16 and dim_head == 64 and N <= cap
 
 
 def attention_fwd(qkv, B, N, H, scale):
-    """qkv bf16 [B, N, 3*H*64] -> (out bf16 [B, N, H*64], lse fp32 [B, H, N])"""
+    """qkv bf16 [B, N, 3*H*64] -> (out bf16 [B, N, H*64], lse fp32 [B, H, N]); N > 320 takes the key-tiled kernel."""
+    if N > ATTN_SHORT_MAX_N:
+        return attention_fwd_long(qkv, B, N, H, scale)
     require_cuda(qkv)
     out = torch.empty(B, N, H * 64, dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
@@ -832,10 +841,32 @@ def attention_fwd(qkv, B, N, H, scale):
 
 
 def attention_bwd(qkv, out, dout, lse, B, N, H, scale, colsum=None):
-    """-> dqkv.  ``colsum`` (optional fp32 [B, 3*H*64]) receives per-image column sums of dqkv (bias-gradient partials)."""
+    """-> dqkv.  ``colsum`` (optional fp32 [B, 3*H*64]) receives per-image column sums of dqkv (bias-gradient partials).
+    N > 320 takes the key-tiled kernels."""
+    if N > ATTN_SHORT_MAX_N:
+        return attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=colsum)
     dqkv = torch.empty_like(qkv)
     check(lib().mv_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(colsum), B, N, H, scale, _s()),
           "attention_bwd", B=B, N=N, H=H)
+    return dqkv
+
+
+def attention_fwd_long(qkv, B, N, H, scale):
+    """The key-tiled forward (any N <= 8192): as ``attention_fwd``."""
+    require_cuda(qkv)
+    out = torch.empty(B, N, H * 64, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    check(lib().mv_attention_fwd_long(_p(qkv), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_long", B=B, N=N, H=H)
+    return out, lse
+
+
+def attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=None):
+    """The key-tiled backward (any N <= 8192): as ``attention_bwd``; the delta workspace is a torch allocation (graph capture)."""
+    require_cuda(qkv, out, dout, lse)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    check(lib().mv_attention_bwd_long(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(colsum), B, N, H, scale,
+                                      _s()), "attention_bwd_long", B=B, N=N, H=H)
     return dqkv
 
 

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""The key-tiled bf16 attention core (N > 320) against the materialised fp32 path it replaces, ViT-B heads (H = 12), GPU.
+
+Per length, alternating in one process (best of ROUNDS): the long forward and backward (ops.attention_fwd_long / _bwd_long),
+the materialised path of functional._AttnBlock (q, k, v cast to fp32, [B, H, N, N] probabilities, the fp32 products, the
+bf16 casts) forward and backward, and at N = 257 the whole-head kernels (mv_attention_fwd / _bwd) that the long ones would
+replace there -- the price of being general.  Algorithmic FLOP: forward 4 B H N^2 64, backward 10 B H N^2 64.
+
+    python tools/bench_attn_long.py [--out FILE]      (prints a table; FILE gets the same table and one JSON line per case)"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "myrtle-vision_amd"))
+import torch  # noqa: E402
+
+from myrtle_vision.hip import ops  # noqa: E402
+
+H, SCALE, ROUNDS = 12, 0.125, 3
+CASES = [(64, 577), (32, 785), (32, 1025), (2, 4097), (64, 257)]
+
+
+def timeit(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters * 1e3          # us
+
+
+def materialised_fwd(qkv, B, N):
+    q32 = ops.cast(qkv, torch.float32)
+    probs = ops.attention_probs_fp32(q32, B, N, H, 64, SCALE)
+    return ops.cast(ops.attention_pv_fp32(probs, q32, B, N, H, 64), torch.bfloat16), probs
+
+
+def materialised_bwd(probs, qkv, dout, B, N):
+    return ops.cast(ops.attention_bwd_fp32(probs, ops.cast(qkv, torch.float32), ops.cast(dout, torch.float32), B, N, H, 64, SCALE),
+                    torch.bfloat16)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines, rows = [], []
+    dev = torch.cuda.get_device_name(0)
+    for B, N in CASES:
+        gen = torch.Generator(device="cuda").manual_seed(N)
+        qkv = (torch.randn(B, N, 3 * H * 64, device="cuda", generator=gen) * 0.8).to(torch.bfloat16)
+        dout = torch.randn(B, N, H * 64, device="cuda", generator=gen).to(torch.bfloat16)
+        out, lse = ops.attention_fwd_long(qkv, B, N, H, SCALE)
+        iters = max(3, min(50, int(2e12 / (10.0 * B * H * N * N * 64) * 20)))
+        arms = {
+            "long_fwd": lambda: ops.attention_fwd_long(qkv, B, N, H, SCALE),
+            "long_bwd": lambda: ops.attention_bwd_long(qkv, out, dout, lse, B, N, H, SCALE),
+        }
+        if N <= ops.ATTN_SHORT_MAX_N:
+            sout, slse = ops.attention_fwd(qkv, B, N, H, SCALE)
+            arms["short_fwd"] = lambda: ops.attention_fwd(qkv, B, N, H, SCALE)
+            arms["short_bwd"] = lambda: ops.attention_bwd(qkv, sout, dout, slse, B, N, H, SCALE)
+        else:
+            mout, probs = materialised_fwd(qkv, B, N)
+            arms["mat_fwd"] = lambda: materialised_fwd(qkv, B, N)
+            arms["mat_bwd"] = lambda: materialised_bwd(probs, qkv, dout, B, N)
+        best = {k: 1e30 for k in arms}
+        for _ in range(ROUNDS):
+            for k, fn in arms.items():
+                best[k] = min(best[k], timeit(fn, iters))
+        fl_f, fl_b = 4.0 * B * H * N * N * 64, 10.0 * B * H * N * N * 64
+        other = "short" if N <= ops.ATTN_SHORT_MAX_N else "mat"
+        rec = {"B": B, "N": N, "H": H, "device": dev, "iters": iters, "rounds": ROUNDS}
+        for k, us in best.items():
+            rec[k + "_us"] = round(us, 1)
+            rec[k + "_tflops"] = round((fl_f if k.endswith("fwd") else fl_b) / us / 1e6, 1)
+        rec["speedup_fwd_bwd"] = round((best[other + "_fwd"] + best[other + "_bwd"]) / (best["long_fwd"] + best["long_bwd"]), 2)
+        lines.append(json.dumps(rec))
+        rows.append(f"| {B:3d} | {N:5d} | {best['long_fwd']:9.1f} ({rec['long_fwd_tflops']:6.1f}) | "
+                    f"{best['long_bwd']:9.1f} ({rec['long_bwd_tflops']:6.1f}) | {other:5s} | "
+                    f"{best[other + '_fwd']:9.1f} ({rec[other + '_fwd_tflops']:6.1f}) | "
+                    f"{best[other + '_bwd']:9.1f} ({rec[other + '_bwd_tflops']:6.1f}) | {rec['speedup_fwd_bwd']:5.2f}x |")
+        print(rows[-1], flush=True)
+        del arms, qkv, dout, out, lse
+        torch.cuda.empty_cache()
+    head = ["| B | N | long fwd us (TFLOP/s) | long bwd us (TFLOP/s) | vs | fwd us (TFLOP/s) | bwd us (TFLOP/s) | fwd+bwd speed-up |",
+            "|---|---|---|---|---|---|---|---|"]
+    text = "\n".join(head + rows) + "\n\n" + "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(f"# tools/bench_attn_long.py on {dev}, ViT-B heads (H = 12), best of {ROUNDS} alternating rounds\n"
+                    "# vs: mat = materialised fp32 path (functional._AttnBlock above 320 tokens before), short = the whole-head kernels\n")
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
