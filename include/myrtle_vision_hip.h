@@ -166,7 +166,7 @@ int mv_attention_fwd_long(const void* qkv, void* out, float* lse, int B, int N, 
 int mv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, float* delta_ws, void* dqkv,
                           float* colsum, int B, int N, int H, float scale, mv_stream_t stream);
 /* The attention core of precision "bf16x3" (vit.py:87-96 between fp32 tensors): the fused kernels above on IEEE-half operands with
- * fp32 accumulation, softmax and OUTPUTS; N <= 288 (N <= 208: the 13-key-tile kernels; above: the two-pass kernels of the 257-token case).  qkv16: half [B, N, 3, H, 64] (mv_cast to MV_F16 of the fp32 to_qkv output);
+ * fp32 accumulation, softmax and OUTPUTS; N <= 288 (longer: mv_attention_fwd_long_f16 below; N <= 208: the 13-key-tile kernels; above: the two-pass kernels of the 257-token case).  qkv16: half [B, N, 3, H, 64] (mv_cast to MV_F16 of the fp32 to_qkv output);
  * out / lse as mv_attention_fwd but out is fp32.  Backward: mv_attention_bwd_prep_f16 turns the fp32 dout [B, N, H*64] into half
  * scaled, per (image, head), by a power of two s (the slice's largest magnitude -> [2^7, 2^8): gradients lie below half's normal
  * range otherwise), leaves s in gscale[b * H + h] (device, fp32 [B * H]) and delta[b, h, n] = sum_d half(dout * s) * out.
@@ -178,6 +178,17 @@ int mv_attention_bwd_prep_f16(const float* dout, const float* out, void* dout16,
                               mv_stream_t stream);
 int mv_attention_bwd_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse, const float* gscale,
                          void* dqkv, int nseg, float* colsum, int B, int N, int H, float scale, mv_stream_t stream);
+/* The same half-operand core for any 1 <= N <= 8192 (precision "bf16x3h" at 384^2 fine-tuning, 577 tokens, and 512^2 segmentation,
+ * 1 025): the key-tiled kernels of mv_attention_fwd_long / _bwd_long on IEEE half, so no [N, N] tensor exists.  Arguments, layouts,
+ * alignment and the roundings as mv_attention_fwd_f16 / mv_attention_bwd_f16 (dout16, delta and gscale from
+ * mv_attention_bwd_prep_f16, which takes any N).  colsum_ws: a caller-provided fp32 workspace of B * ceil(N / 128) * 3 * H * 64
+ * floats, needed only with colsum: every 128-row block of keys and of queries leaves the column sums of its fp32 dqkv rows there,
+ * and a fixed-order pass adds them into colsum.  Deterministic: no atomics, every output has one owner.  ops.attention_fwd_f16 /
+ * _bwd_f16 take these for N > 288 and the kernels above otherwise. */
+int mv_attention_fwd_long_f16(const void* qkv16, float* out, float* lse, int B, int N, int H, float scale, mv_stream_t stream);
+int mv_attention_bwd_long_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse, const float* gscale,
+                              void* dqkv, int nseg, float* colsum, float* colsum_ws, int B, int N, int H, float scale,
+                              mv_stream_t stream);
 /* Test / tuning hook (process-global, atomic, like mv_gemm_force_variant): backward kernel for the following
  * mv_attention_bwd calls -- 0 auto (N <= 208: 4; N <= 288: 2; else 8), 4 = dS exchanged through LDS (N <= 208), 5 = the same
  * with two waves of 512 registers per workgroup (192 < N <= 208; equal results up to the placement of the softmax scale), 2 = two

@@ -1579,12 +1579,43 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2p_kernel(const bf16_t* __rest
 // S and dP are computed twice (seven products instead of five); in exchange every output has exactly one owner: no atomics, no
 // cross-workgroup order, bitwise reproducible.  delta = rowsum(dO * O) comes from attn_delta_long_kernel (workspace [B, H, N]),
 // the to_qkv bias-gradient column sums from attn_colsum_long_kernel: a fixed-order pass over the rounded dqkv.
-// F16 selects the matrix instruction and the P / dS rounding (mma32 / pack8t); a half instantiation would add its fp32 stores.
+// F16 selects the matrix instruction and the P / dS rounding (mma32 / pack8t).  F16 = true is the attention core of precision
+// "bf16x3h" past 288 tokens (mv_attention_fwd_long_f16 / _bwd_long_f16), with the conventions of attn_fwd13_kernel<true> and
+// attn_bwd2p_kernel<9, true, SPLIT>: half q / k / v, fp32 out; backward on dO16 = dO * gscale (a power of two per (image, head))
+// with delta from attn_bwd_prep_f16_kernel, dS formed without the softmax scale and clamped to half's range, the scale and
+// 1 / gscale applied to the fp32 accumulators at the store (exact for gscale); SPLIT = 0 writes fp32 dqkv, SPLIT = 3 / 6 the bf16
+// pieces of exactly those values (attn_put4_f16).  Column sums: every dK / dV and dQ workgroup writes the sums of its own 128 rows
+// of the fp32 values to a workspace [B, nblk, 3 D]; attn_colsum_ws_kernel adds the nblk partials in order.
 constexpr int ATTN_LONG_MAX_N = 8192;
 constexpr int LQB = 128;     // queries per forward / dQ workgroup (4 waves x 32)
 constexpr int LKB = 128;     // keys per dK / dV workgroup (4 waves x 32)
 constexpr int LBLK = 64;     // rows per streamed LDS block
 constexpr int LSTAGE = 2 * LBLK * 128;   // one ring stage: two [64][64] bf16 sw128 images = 16 KiB
+static_assert(LQB == LKB, "the F16 column-sum workspace has one [3 D] row per 128-row block of queries and of keys");
+
+// F16 outputs of the long backward: four consecutive fp32 features v at (row = b N + token, col < 3 D) of dqkv [B N, 3 D] (SPLIT = 0),
+// or their bf16 pieces in rows of SPLIT * 3 D, segments 3 D apart (mv_split2_bf16 / mv_split3_bf16 role 0) -- attn_bwd2p_kernel's put4
+template <int SPLIT>
+__device__ __forceinline__ void attn_put4_f16(bf16_t* __restrict__ dqkv, long row, long col, long C, f32x4 v) {
+  if constexpr (SPLIT == 0) {
+    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(dqkv) + row * C + col) = v;
+  } else {
+    bf16_t* o = dqkv + row * (SPLIT * C) + col;
+    bf16x4 p[3];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bf16_t p0 = (bf16_t)v[e];
+      const float r1 = v[e] - (float)p0;
+      const bf16_t p1 = (bf16_t)r1;
+      p[0][e] = p0;
+      p[1][e] = p1;
+      p[2][e] = (bf16_t)(r1 - (float)p1);
+    }
+    constexpr int order[6] = {0, 0, 1, 0, 1, 2};
+#pragma unroll
+    for (int sg = 0; sg < SPLIT; ++sg) *reinterpret_cast<bf16x4*>(o + (long)sg * C) = p[order[sg]];
+  }
+}
 
 // rows row0 .. row0 + 63 of a [*, ld] bf16 tensor (64 features from src) -> a [64][64] sw128 image: 8 pieces of 8 rows, two per
 // wave; rows >= N clamped to N - 1 (masked by the caller).  The DMA is hidden from the compiler's wait bookkeeping (glds16_hidden):
@@ -1703,12 +1734,21 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const bf16_t* __r
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[t][dt] *= inv;
     const int qrow = q0 + 16 * t + (lane & 15);
+    if constexpr (F16) {                               // fp32 output: the lane's four features of each 16-feature tile
+      if (qrow < N) {
+        float* orow = reinterpret_cast<float*>(out) + ((long)b * N + qrow) * D + h * 64;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(orow + 16 * dt + 4 * g) = o[t][dt];
+        if (g == 0) lse[((long)b * H + h) * N + qrow] = (m[t] + __builtin_amdgcn_logf(s)) * LN2;
+      }
+    } else {
     const u32x4 w0 = pair16(o[t][0], o[t][1]), w1 = pair16(o[t][2], o[t][3]);     // every lane (lane exchange)
     if (qrow < N) {
       bf16_t* orow = out + ((long)b * N + qrow) * D + h * 64;
       *reinterpret_cast<u32x4*>(orow + pair16_off(0, g)) = w0;
       *reinterpret_cast<u32x4*>(orow + pair16_off(2, g)) = w1;
       if (g == 0) lse[((long)b * H + h) * N + qrow] = (m[t] + __builtin_amdgcn_logf(s)) * LN2;
+    }
     }
   }
 }
@@ -1735,10 +1775,12 @@ __global__ __launch_bounds__(256) void attn_delta_long_kernel(const bf16_t* __re
   }
 }
 
-template <bool F16 = false>
+template <bool F16 = false, int SPLIT = 0>   // F16: dout = dO16 (scaled by gscale), dqkv fp32 or SPLIT pieces, colsum_ws partials
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                                     const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                    bf16_t* __restrict__ dqkv, int N, int H, int nkb, float scale) {
+                                                                    bf16_t* __restrict__ dqkv, int N, int H, int nkb, float scale,
+                                                                    const float* __restrict__ gscale = nullptr,
+                                                                    float* __restrict__ colsum_ws = nullptr) {
   __shared__ __attribute__((aligned(16))) char smem[2 * LSTAGE];    // stage s: Q [64][64] | dO [64][64]
   __shared__ __attribute__((aligned(16))) float sRow[2][2][LBLK];    // stage s: lse * log2(e) (+inf past N) | delta (0 past N)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
@@ -1843,7 +1885,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_long_kernel(const bf16_t
               float p = __builtin_amdgcn_exp2f(sv[r] * c2 - l2v[t][r]);     // queries >= N: lse = +inf -> p = 0
               p = key < N ? p : 0.f;
               pp[t][r] = p;
-              ds[t][r] = p * (dp[r] - dlv[t][r]) * scale;
+              ds[t][r] = F16 ? __builtin_amdgcn_fmed3f(p * (dp[r] - dlv[t][r]), -65000.f, 65000.f) : p * (dp[r] - dlv[t][r]) * scale;
             }
           }
           const bf16x8 pf = pack8t<F16>(pp[0], pp[1]);
@@ -1860,6 +1902,42 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_long_kernel(const bf16_t
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
+  if constexpr (F16) {
+    const float inv_s = 1.0f / gscale[bh], inv_ss = inv_s * scale;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        adk[i][dt] *= inv_ss;
+        adv[i][dt] *= inv_s;
+      }
+      const int key = k0 + 16 * i + (lane & 15);
+      if (key < N) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          attn_put4_f16<SPLIT>(dqkv, (long)b * N + key, D + h * 64 + 16 * dt + 4 * g, 3 * D, adk[i][dt]);
+          attn_put4_f16<SPLIT>(dqkv, (long)b * N + key, 2 * D + h * 64 + 16 * dt + 4 * g, 3 * D, adv[i][dt]);
+        }
+      }
+    }
+    if (colsum_ws) {                                   // padded keys and idle waves: exact zeros
+      float* sCs = reinterpret_cast<float*>(smem);     // [4 waves][dK 64 | dV 64]; the ring is idle after the last barrier
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float vk = rowsum16(adk[0][dt][r] + adk[1][dt][r]), vv = rowsum16(adv[0][dt][r] + adv[1][dt][r]);
+          if ((lane & 15) == 0) {
+            sCs[wave * 128 + dt * 16 + 4 * g + r] = vk;
+            sCs[wave * 128 + 64 + dt * 16 + 4 * g + r] = vv;
+          }
+        }
+      __syncthreads();
+      if (tid < 128)
+        colsum_ws[((long)b * nkb + kblk) * 3 * D + (1 + (tid >> 6)) * D + h * 64 + (tid & 63)] =
+            ((sCs[tid] + sCs[128 + tid]) + sCs[256 + tid]) + sCs[384 + tid];
+    }
+  } else {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int key = k0 + 16 * i + (lane & 15);
@@ -1872,12 +1950,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_long_kernel(const bf16_t
       }
     }
   }
+  }
 }
 
-template <bool F16 = false>
+template <bool F16 = false, int SPLIT = 0>   // F16: as attn_bwd_dkdv_long_kernel
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                  bf16_t* __restrict__ dqkv, int N, int H, int nqb, float scale) {
+                                                                  bf16_t* __restrict__ dqkv, int N, int H, int nqb, float scale,
+                                                                  const float* __restrict__ gscale = nullptr,
+                                                                  float* __restrict__ colsum_ws = nullptr) {
   __shared__ __attribute__((aligned(16))) char smem[2 * LSTAGE];    // stage s: K [64][64] | V [64][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
   const LaneOff L = make_lane_off(lane);
@@ -1951,7 +2032,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_long_kernel(const bf16_t* 
             for (int r = 0; r < 4; ++r) {
               const int key = kb * LBLK + 32 * u + 16 * kk + 4 * g + r;
               const float p = key < N ? __builtin_amdgcn_exp2f(st[r] * c2 - l2[t]) : 0.f;
-              ds[kk][r] = p * (dp[r] - dl[t]) * scale;
+              ds[kk][r] = F16 ? __builtin_amdgcn_fmed3f(p * (dp[r] - dl[t]), -65000.f, 65000.f) : p * (dp[r] - dl[t]) * scale;
             }
           }
           const bf16x8 dsf = pack8t<F16>(ds[0], ds[1]);
@@ -1963,6 +2044,32 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_long_kernel(const bf16_t* 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
+  if constexpr (F16) {
+    const float inv_ss = 1.0f / gscale[bh] * scale;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) dq[t][dt] *= inv_ss;
+      const int qrow = q0 + 16 * t + (lane & 15);
+      if (qrow < N) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) attn_put4_f16<SPLIT>(dqkv, (long)b * N + qrow, h * 64 + 16 * dt + 4 * g, 3 * D, dq[t][dt]);
+      }
+    }
+    if (colsum_ws) {                                   // padded queries (lse = +inf) and idle waves: exact zeros
+      float* sCs = reinterpret_cast<float*>(smem);     // [4 waves][dQ 64]; the ring is idle after the last barrier
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float vq = rowsum16(dq[0][dt][r] + dq[1][dt][r]);
+          if ((lane & 15) == 0) sCs[wave * 64 + dt * 16 + 4 * g + r] = vq;
+        }
+      __syncthreads();
+      if (tid < 64)
+        colsum_ws[((long)b * nqb + qblk) * 3 * D + h * 64 + tid] = ((sCs[tid] + sCs[64 + tid]) + sCs[128 + tid]) + sCs[192 + tid];
+    }
+  } else {
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int qrow = q0 + 16 * t + (lane & 15);
@@ -1972,6 +2079,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_long_kernel(const bf16_t* 
       *reinterpret_cast<u32x4*>(drow + pair16_off(0, g)) = w0;
       *reinterpret_cast<u32x4*>(drow + pair16_off(2, g)) = w1;
     }
+  }
   }
 }
 
@@ -2001,6 +2109,18 @@ __global__ __launch_bounds__(256) void attn_colsum_long_kernel(const bf16_t* __r
     for (int k = 0; k < 8; ++k) s += red[k][tid];
     colsum[(long)b * C + cc] = s;
   }
+}
+
+// colsum[b][c] = sum_k ws[b][k][c] over the nblk row-block partials of the F16 long backward, k = 0, 1, ... in order
+__global__ __launch_bounds__(256) void attn_colsum_ws_kernel(const float* __restrict__ ws, float* __restrict__ colsum, int nblk, int C,
+                                                             long total) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;     // = b C + c
+  if (idx >= total) return;
+  const long b = idx / C, c = idx % C;
+  const float* p = ws + b * nblk * C + c;
+  float s = 0.f;
+  for (int k = 0; k < nblk; ++k) s += p[(long)k * C];
+  colsum[idx] = s;
 }
 
 template <typename K>
@@ -2274,6 +2394,50 @@ extern "C" int mv_attention_bwd_long(const void* qkv, const void* out, const voi
     const int C = 3 * H * 64;
     attn_colsum_long_kernel<<<dim3((C + 255) / 256, B), 256, 0, s>>>((const bf16_t*)dqkv, colsum, N, C);
   }
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// precision "bf16x3h" past 288 tokens: the key-tiled kernels on IEEE-half operands (ops.attention_fwd_f16 / _bwd_f16 route
+// N > 288 here); any 1 <= N <= ATTN_LONG_MAX_N
+// ------------------------------------------------------------------------------------------------
+extern "C" int mv_attention_fwd_long_f16(const void* qkv16, float* out, float* lse, int B, int N, int H, float scale,
+                                         mv_stream_t stream) {
+  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && N <= ATTN_LONG_MAX_N, MV_ERR_SHAPE);
+  const long nqb = (N + LQB - 1) / LQB;
+  MV_REQUIRE(nqb * B * H < (1L << 31), MV_ERR_SHAPE);
+  MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(out) && lse, MV_ERR_ALIGN);
+  if (B == 0) return MV_OK;
+  attn_fwd_long_kernel<true><<<(unsigned)(nqb * B * H), 256, 0, (hipStream_t)stream>>>(
+      (const bf16_t*)qkv16, (bf16_t*)out, lse, N, H, (int)nqb, scale * LOG2E);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+extern "C" int mv_attention_bwd_long_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse,
+                                         const float* gscale, void* dqkv, int nseg, float* colsum, float* colsum_ws, int B, int N,
+                                         int H, float scale, mv_stream_t stream) {
+  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && N <= ATTN_LONG_MAX_N, MV_ERR_SHAPE);
+  MV_REQUIRE(nseg == 0 || nseg == 3 || nseg == 6, MV_ERR_UNSUPPORTED);
+  const long nb = (N + LQB - 1) / LQB, C = 3L * H * 64;
+  MV_REQUIRE(nb * B * H < (1L << 31) && ((long)B * C + 255) / 256 < (1L << 31), MV_ERR_SHAPE);
+  MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(dout16) && mv_aligned16(dqkv) && delta && lse && gscale && (!colsum || colsum_ws),
+             MV_ERR_ALIGN);
+  if (B == 0) return MV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = colsum ? colsum_ws : nullptr;
+#define MV_BWD_LONG_F16(SPLIT_)                                                                                                 \
+  {                                                                                                                            \
+    attn_bwd_dkdv_long_kernel<true, SPLIT_><<<(unsigned)(nb * B * H), 256, 0, s>>>(                                            \
+        (const bf16_t*)qkv16, (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, (int)nb, scale, gscale, ws);             \
+    attn_bwd_dq_long_kernel<true, SPLIT_><<<(unsigned)(nb * B * H), 256, 0, s>>>(                                              \
+        (const bf16_t*)qkv16, (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, (int)nb, scale, gscale, ws);             \
+  }
+  if (nseg == 0) MV_BWD_LONG_F16(0) else if (nseg == 3) MV_BWD_LONG_F16(3) else MV_BWD_LONG_F16(6)
+#undef MV_BWD_LONG_F16
+  if (colsum)
+    attn_colsum_ws_kernel<<<(unsigned)(((long)B * C + 255) / 256), 256, 0, s>>>(ws, colsum, (int)nb, (int)C, (long)B * C);
   MV_CHECK_LAUNCH();
   return MV_OK;
 }

@@ -11,7 +11,8 @@ every nn.Linear product to 2^-16 relative instead of 2^-25 (two bf16 pieces per 
 of bf16x6; attention core, LayerNorm, GELU, softmax and the residual stream exactly as in ``"fp32"``) -- the cheapest arithmetic
 inside BASELINE's 1e-3 end to end; ``"bf16x3h"`` = bf16x3 with the attention core on IEEE-half operands (the fused bf16 kernels
 templated on the element type, fp32 sums / softmax / outputs): logits still 7x inside 1e-3 and every arg-max exact, gradients to
-1.6e-3 (twelve layers of 2^-12 roundings of q and k under the exponential), 20 % faster than bf16x3.
+1.6e-3 (twelve layers of 2^-12 roundings of q and k under the exponential), 20 % faster than bf16x3.  The half core covers any
+sequence up to 8 192 tokens: the whole-head kernels up to 288, the key-tiled ones above (384^2 fine-tuning, 512^2 segmentation).
 """
 import ctypes
 import os
@@ -819,8 +820,10 @@ def colsum(x, rows, cols, ld, out):
 # attention
 # ------------------------------------------------------------------------------------------------------------
 ATTN_SHORT_MAX_N = 320      # the whole-head kernels (mv_attention_fwd / _bwd): K and V of a head in LDS
-ATTN_LONG_MAX_N = 8192      # the key-tiled kernels (mv_attention_fwd_long / _bwd_long)
-# A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320 back to the materialised fp32 path
+ATTN_LONG_MAX_N = 8192      # the key-tiled kernels (mv_attention_fwd_long / _bwd_long, and their half forms _long_f16)
+ATTN_F16_SHORT_MAX_N = 288  # the whole-head half kernels (mv_attention_fwd_f16 / _bwd_f16)
+# A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320 and the half attention of bf16x3h with
+# N > 288 back to the materialised fp32 path
 ATTN_LONG = True
 
 
@@ -875,8 +878,10 @@ def attention_f32_fused_supported(qkv_dtype, N, dim_head):
 
 
 def attention_f16_supported(qkv_dtype, N, dim_head):
-    """The half-operand attention core of precision "bf16x3h" (the bf16 kernels instantiated on IEEE half): fp32 q/k/v, N <= 288."""
-    return qkv_dtype == torch.float32 and dim_head == 64 and N <= 288 and half_attention()
+    """The half-operand attention core of precision "bf16x3h" (the bf16 kernels instantiated on IEEE half): fp32 q/k/v, N <= 8192
+    (the whole-head kernels up to 288 tokens, the key-tiled ones above; 288 with ``ATTN_LONG`` off)."""
+    cap = ATTN_LONG_MAX_N if ATTN_LONG else ATTN_F16_SHORT_MAX_N
+    return qkv_dtype == torch.float32 and dim_head == 64 and N <= cap and half_attention()
 
 
 def cast_f16(src):
@@ -888,7 +893,9 @@ def cast_f16(src):
 
 
 def attention_fwd_f16(qkv16, B, N, H, scale):
-    """-> (out fp32 [B, N, H*64], lse fp32 [B, H, N]) from half q/k/v [B, N, 3, H, 64]."""
+    """-> (out fp32 [B, N, H*64], lse fp32 [B, H, N]) from half q/k/v [B, N, 3, H, 64]; N > 288 takes the key-tiled kernel."""
+    if N > ATTN_F16_SHORT_MAX_N:
+        return attention_fwd_long_f16(qkv16, B, N, H, scale)
     out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv16.device)
     lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv16.device)
     check(lib().mv_attention_fwd_f16(_p(qkv16), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_f16", B=B, N=N, H=H)
@@ -899,17 +906,51 @@ def attention_bwd_f16(qkv16, out, dout, lse, B, N, H, scale, split=False, colsum
     """-> dqkv [B, N, 3*H*64]: fp32, or (``split``) its bf16 pieces [B * N, nseg * 3*H*64] for the to_qkv dW / dX products.  ``out``
     / ``dout`` fp32 [B, N, H*64]: dout is scaled into half's range per (image, head) by a power of two taken from its own largest
     magnitude (one pass that also leaves delta); the kernel divides the factor out of its outputs.  ``colsum``: fp32 [B, 3*H*64]
-    receiving per-image column sums of dqkv (to_qkv's bias gradient after a sum over images)."""
+    receiving per-image column sums of dqkv (to_qkv's bias gradient after a sum over images).  N > 288 takes the key-tiled
+    kernels."""
+    if N > ATTN_F16_SHORT_MAX_N:
+        return attention_bwd_long_f16(qkv16, out, dout, lse, B, N, H, scale, split=split, colsum=colsum)
     dev = qkv16.device
+    dout16, delta, gscale = _attention_bwd_prep_f16(out, dout, B, N, H)
+    nseg = current_segments() if split else 0
+    dqkv = _split_buffer(B * N, 3 * H * 64, dev) if split else torch.empty(B, N, 3 * H * 64, dtype=torch.float32, device=dev)
+    check(lib().mv_attention_bwd_f16(_p(qkv16), _p(dout16), _p(delta), _p(lse), _p(gscale), _p(dqkv), nseg, _p(colsum), B, N, H,
+                                     scale, _s()), "attention_bwd_f16", B=B, N=N, H=H)
+    return dqkv
+
+
+def _attention_bwd_prep_f16(out, dout, B, N, H):
+    """dout fp32 -> (dout16 half scaled per (image, head) by gscale, delta = rowsum(dout16 * out), gscale fp32 [B * H])."""
+    dev = out.device
     dout16 = torch.empty(B, N, H * 64, dtype=torch.float16, device=dev)
     delta = torch.empty(B, H, N, dtype=torch.float32, device=dev)
     gscale = torch.empty(B * H, dtype=torch.float32, device=dev)
     check(lib().mv_attention_bwd_prep_f16(_p(dout), _p(out), _p(dout16), _p(delta), _p(gscale), B, N, H, _s()),
           "attention_bwd_prep_f16", B=B, N=N, H=H)
+    return dout16, delta, gscale
+
+
+def attention_fwd_long_f16(qkv16, B, N, H, scale):
+    """The key-tiled half forward (any N <= 8192): as ``attention_fwd_f16``."""
+    require_cuda(qkv16)
+    out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv16.device)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv16.device)
+    check(lib().mv_attention_fwd_long_f16(_p(qkv16), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_long_f16",
+          B=B, N=N, H=H)
+    return out, lse
+
+
+def attention_bwd_long_f16(qkv16, out, dout, lse, B, N, H, scale, split=False, colsum=None):
+    """The key-tiled half backward (any N <= 8192): as ``attention_bwd_f16``.  With ``colsum`` the per-block column-sum workspace
+    [B, ceil(N / 128), 3*H*64] is a torch allocation, like the prep outputs (graph capture)."""
+    require_cuda(qkv16, out, dout, lse)
+    dev = qkv16.device
+    dout16, delta, gscale = _attention_bwd_prep_f16(out, dout, B, N, H)
     nseg = current_segments() if split else 0
     dqkv = _split_buffer(B * N, 3 * H * 64, dev) if split else torch.empty(B, N, 3 * H * 64, dtype=torch.float32, device=dev)
-    check(lib().mv_attention_bwd_f16(_p(qkv16), _p(dout16), _p(delta), _p(lse), _p(gscale), _p(dqkv), nseg, _p(colsum), B, N, H,
-                                     scale, _s()), "attention_bwd_f16", B=B, N=N, H=H)
+    ws = torch.empty(B, (N + 127) // 128, 3 * H * 64, dtype=torch.float32, device=dev) if colsum is not None else None
+    check(lib().mv_attention_bwd_long_f16(_p(qkv16), _p(dout16), _p(delta), _p(lse), _p(gscale), _p(dqkv), nseg, _p(colsum),
+                                          _p(ws), B, N, H, scale, _s()), "attention_bwd_long_f16", B=B, N=N, H=H)
     return dqkv
 
 

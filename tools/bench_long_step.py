@@ -2,9 +2,10 @@
 """ViT-B/16 at 384^2 (577 tokens), batch 64, bf16 training step: the key-tiled attention kernels (ops.ATTN_LONG = True, the
 default) against the materialised fp32 attention the step took before (False), alternating in blocks of STEPS steps for ROUNDS
 rounds in one process.  Per arm: ms/step (mean, std, min over blocks), img/s and torch.cuda.max_memory_allocated over the arm's
-blocks.
+blocks.  PRECISION=bf16x3h (or any other ViT precision; default bf16) runs that precision's step instead: for bf16x3h the arms
+are the key-tiled half kernels against the materialised fp32 path; the lines then carry a "precision" field.
 
-    ROUNDS=4 STEPS=5 python tools/bench_long_step.py [--out FILE]"""
+    ROUNDS=4 STEPS=5 [PRECISION=bf16x3h] python tools/bench_long_step.py [--out FILE]"""
 import argparse
 import json
 import os
@@ -22,6 +23,7 @@ from myrtle_vision.utils.optim import AdamW, ParamArena  # noqa: E402
 from myrtle_vision.utils.utils import seed_everything  # noqa: E402
 
 ROUNDS, STEPS, BATCH, SIZE = int(os.environ.get("ROUNDS", 4)), int(os.environ.get("STEPS", 5)), int(os.environ.get("BATCH", 64)), 384
+PRECISION = os.environ.get("PRECISION", "bf16")
 
 
 def main():
@@ -31,7 +33,7 @@ def main():
     dev = torch.device("cuda", 0)
     seed_everything(1234)
     vit = ViT(decoder="classification", image_size=SIZE, patch_size=16, num_classes=1000, dim=768, depth=12, heads=12,
-              mlp_dim=3072, precision="bf16", q_format="FP32").to(dev)
+              mlp_dim=3072, precision=PRECISION, q_format="FP32").to(dev)
     opt = AdamW(ParamArena(vit.named_parameters(), skip=vit.unused_parameter_names()), lr=6.25e-5, weight_decay=0.05)
     g = torch.Generator().manual_seed(1234)
     img = torch.randn(BATCH, 3, SIZE, SIZE, generator=g).to(dev)
@@ -73,6 +75,8 @@ def main():
                "std": round(statistics.pstdev(t), 2), "min": round(min(t), 2), "img_per_s": round(BATCH / statistics.mean(t) * 1e3, 1),
                "max_memory_allocated_GB": round(peak[k] / 1e9, 2), "blocks": f"{ROUNDS} x {STEPS} steps",
                "device": torch.cuda.get_device_name(0)}
+        if PRECISION != "bf16":
+            rec["precision"] = PRECISION
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
     if args.out:
