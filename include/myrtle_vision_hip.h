@@ -356,6 +356,18 @@ int mv_layernorm_fwd_q8(const float* x, long ldx, const float* gamma, const floa
                         float eps, float scale, int zero_point, mv_stream_t stream);
 int mv_attention_fwd_f32_q8(const float* qkv, void* codes, int B, int N, int H, float scale, float q_scale, int q_zero_point,
                             mv_stream_t stream);
+/* The exact-fp32 attention core (Attention.forward vit.py:87-96) for any 1 <= N <= 8192 (384^2 fine-tuning: 577 tokens, 512^2
+ * segmentation: 1 025): key-tiled kernels on the same f32-input matrix cores, so no [N, N] tensor exists in either direction.
+ * Layouts, arithmetic and outputs as mv_attention_fwd_f32 (lse == NULL: evaluation), mv_attention_fwd_f32_lse, mv_attention_fwd_f32_q8
+ * (codes bit-identical to mv_attention_fwd_long_f32 + mv_quant_affine_i8) and mv_attention_bwd_f32; the online softmax sums in
+ * another order.  delta_ws: a caller-provided fp32 workspace of B * H * N floats (rowsum(dout * out)), required.  Deterministic: no
+ * atomics, every output element has one owner.  MV_ERR_UNSUPPORTED for N > 8192 or a zero point outside 0..255.
+ * ops.attention_fwd_f32 / _f32_lse / _f32_q8 / attention_bwd_f32_fused take these for N > 272 and the kernels above otherwise. */
+int mv_attention_fwd_long_f32(const float* qkv, float* out, float* lse, int B, int N, int H, float scale, mv_stream_t stream);
+int mv_attention_fwd_long_f32_q8(const float* qkv, void* codes, int B, int N, int H, float scale, float q_scale,
+                                 int q_zero_point, mv_stream_t stream);
+int mv_attention_bwd_long_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* delta_ws,
+                              float* dqkv, int B, int N, int H, float scale, mv_stream_t stream);
 /* running min/max observer: minmax[0] = min(minmax[0], min x), minmax[1] = max(minmax[1], max x);
  * minmax points at FOUR floats: [2..3] are scratch for the reduction */
 int mv_minmax(const float* x, long n, float* minmax, mv_stream_t stream);

@@ -458,6 +458,448 @@ int launch_attn_f32(const float* qkv, void* out, int B, int N, int H, float scal
   return MV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// N > 272: key-tiled kernels of the same core (mv_attention_fwd_long_f32 / _q8, mv_attention_bwd_long_f32), any 1 <= N <= 8192
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernels above hold a head's whole K and V^T in LDS and stop at 272 tokens; at 577 (384^2 fine-tuning) or 1 025 (512^2
+// segmentation) the fp32 and bf16x3 modes fell back to the materialised path and its [B, H, N, N] probability tensor.  Here the
+// operands that are swept stream through LDS in 64-row blocks, a two-stage ring loaded one block ahead (the global loads are
+// issued before a block's products, written to the other stage after them, one barrier per block), and nothing of size N^2
+// exists.  A workgroup is 8 waves that each own one 16-row tile: 128 queries (forward, dQ) or keys (dK / dV).
+//   forward : S^T = K_blk Q^T and O^T = V^T_blk P^T in the orientation of attn_fwd_f32_kernel (a lane holds one query; P is the
+//             B operand straight from the registers), with an online softmax in fp32: running maximum m, lane-local running sum,
+//             O^T *= exp2(m_old - m_new) per block, O divided by the sum once at the end.  Keys >= N of the last block are -inf.
+//             The 64-key V^T block has K's row length, so it takes K's slot swizzle (XOR with row & 15): its fragment reads are
+//             then exactly the K reads, conflict-free under the b128 rules (vt_sw above is for rows of NK = 208 / 272 floats).
+//   dK / dV : a wave owns 16 keys (K, V fragments and dK, dV accumulators in registers) and sweeps the query blocks (Q, dO in
+//             LDS): pass B of attn_bwd_f32_kernel, with lse and delta of the block staged beside them.
+//   dQ      : a wave owns 16 queries (Q, dO fragments in registers) and sweeps the key blocks (K, V in LDS): its pass A.
+// delta = rowsum(dO * O) comes from attn_delta_long_f32_kernel (workspace [B, H, N]).  Every output element has one owner:
+// no atomics, bitwise reproducible.  The rows contracted in dV, dK and dQ are read from the row-major images as 4-byte LDS
+// loads (attn_bwd_f32_kernel's elem): at the f32 matrix rate one ds_read_b32 per MFMA is free, and nothing is transposed.
+constexpr int LF_MAX_N = 8192;
+constexpr int LF_ROWS = 128;                  // queries / keys owned by a workgroup (8 waves x 16)
+constexpr int LF_BLK = 64;                    // rows per streamed block
+constexpr int LF_STAGE = 2 * LF_BLK * AF_DH;  // floats per ring stage: two [64][64] fp32 images = 32 KiB
+constexpr int LF_OUT_PLAIN = 0, LF_OUT_LSE = 1, LF_OUT_Q8 = 2;
+
+// rows row0 .. row0 + 63 of a [*, ld] fp32 tensor (64 features at src): two 16-byte pieces per thread, zero past N
+__device__ __forceinline__ void lf_load_rows(f32x4 (&dst)[2], const float* src, long ld, int row0, int N, int tid) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int i = tid + 512 * it, r = row0 + (i >> 4);
+    dst[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (r < N) dst[it] = *reinterpret_cast<const f32x4*>(src + (long)r * ld + 4 * (i & 15));
+  }
+}
+// ... into a [64][64] image with the 16-byte slot XORed with row & 15 (the K image of attn_fwd_f32_kernel)
+__device__ __forceinline__ void lf_write_rows(float* dst, const f32x4 (&v)[2], int tid) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int i = tid + 512 * it, r = i >> 4, j = i & 15;
+    *reinterpret_cast<f32x4*>(dst + r * AF_DH + ((j ^ (r & 15)) << 2)) = v[it];
+  }
+}
+// A-operand fragments of the 16 rows of tile T of a row image: lane (row q16, group g) gets floats 16 c + 4 g .. + 3
+__device__ __forceinline__ void lf_frag_rows(f32x4 (&dst)[4], const float* R, int T, int q16, int g) {
+  const int r = T * 16 + q16;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) dst[c] = *reinterpret_cast<const f32x4*>(R + r * AF_DH + (((4 * c + g) ^ (r & 15)) << 2));
+}
+// B operand of the products that contract over ROWS of a row image: element (row 16 T + 4 g + r, column 16 dt + q16)
+__device__ __forceinline__ float lf_elem(const float* R, int T, int r, int dt, int q16, int g) {
+  const int rr = T * 16 + 4 * g + r, d = 16 * dt + q16;
+  return R[rr * AF_DH + ((((d >> 2) ^ (rr & 15)) << 2) | (d & 3))];
+}
+
+template <int OUT>
+__global__ __launch_bounds__(512) void attn_fwd_long_f32_kernel(const float* __restrict__ qkv, void* __restrict__ out,
+                                                                float* __restrict__ lse, int N, int H, int nqb, float sl2,
+                                                                float q_inv, float q_zp) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];     // stage s: K [64][64] | V^T [64][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15, g = lane >> 4;
+  const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
+  const int b = bh / H, h = bh % H;
+  const long row = 3L * H * AF_DH, orow = (long)H * AF_DH;
+  const float* const qb = qkv + (long)b * N * row + (long)h * AF_DH;
+  const float* const kb = qb + orow;
+  const float* const vb = kb + orow;
+  const int nkb = (N + LF_BLK - 1) / LF_BLK;
+
+  // K rows as lf_load_rows; V with the lanes walking the keys, so that the transposed LDS writes are conflict-free
+  f32x4 kst[2], vst[2];
+  auto issue = [&](int blk) {
+    lf_load_rows(kst, kb, row, blk * LF_BLK, N, tid);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int i = tid + 512 * it, key = blk * LF_BLK + (i & 63);
+      vst[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (key < N) vst[it] = *reinterpret_cast<const f32x4*>(vb + (long)key * row + 4 * (i >> 6));
+    }
+  };
+  auto write = [&](int blk) {
+    float* const Ks = smem + (blk & 1) * LF_STAGE;
+    float* const Vt = Ks + LF_BLK * AF_DH;
+    lf_write_rows(Ks, kst, tid);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int i = tid + 512 * it, key = i & 63, j = i >> 6;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int d = 4 * j + e;
+        Vt[d * LF_BLK + (((key >> 2) ^ (d & 15)) << 2) + (key & 3)] = vst[it][e];
+      }
+    }
+  };
+  issue(0);
+  write(0);
+
+  const int q0 = qblk * LF_ROWS + 16 * wave, q = q0 + q16;
+  const bool active = q0 < N;                  // wave-uniform; an idle wave still stages and meets the barriers
+  f32x4 qf[4];
+  {
+    const float* qrow = qb + (long)(q < N ? q : N - 1) * row + 4 * g;     // clamped: rows >= N are never stored
+#pragma unroll
+    for (int c = 0; c < 4; ++c) qf[c] = *reinterpret_cast<const f32x4*>(qrow + 16 * c);
+  }
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;                // l: this lane's share of the running sum (its four keys per tile)
+  __syncthreads();
+
+  for (int blk = 0; blk < nkb; ++blk) {
+    const bool has_next = blk + 1 < nkb;       // workgroup-uniform
+    if (has_next) issue(blk + 1);
+    if (active) {
+      const float* const Ks = smem + (blk & 1) * LF_STAGE;
+      const float* const Vt = Ks + LF_BLK * AF_DH;
+      // ---- S^T = K Q^T: st[T][r] = score of (query q, key 64 blk + 16 T + 4 g + r), in log2 units
+      f32x4 st[4];
+#pragma unroll
+      for (int T = 0; T < 4; ++T) {
+        f32x4 kf[4];
+        lf_frag_rows(kf, Ks, T, q16, g);
+        st[T] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) st[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[c][kk], qf[c][kk], st[T], 0, 0, 0);
+      }
+      // ---- online softmax
+      float mb = -INFINITY;
+#pragma unroll
+      for (int T = 0; T < 4; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = blk * LF_BLK + T * 16 + 4 * g + r;
+          const float x = key < N ? st[T][r] * sl2 : -INFINITY;
+          st[T][r] = x;
+          mb = fmaxf(mb, x);
+        }
+      mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+      mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+      const float mn = fmaxf(m, mb);           // finite: block 0 holds key 0
+      const float alpha = __builtin_amdgcn_exp2f(m - mn);      // exp2(-inf) = 0 on the first block
+      m = mn;
+      float s = l * alpha;
+#pragma unroll
+      for (int T = 0; T < 4; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(st[T][r] - mn);     // 0 for the keys past N
+          st[T][r] = p;
+          s += p;
+        }
+      l = s;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+      // ---- O^T += V^T P^T: o[dt][r] = out(query q, feature 16 dt + 4 g + r)
+#pragma unroll
+      for (int T = 0; T < 4; ++T) {
+        f32x4 vf[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const int d = dt * 16 + q16;
+          vf[dt] = *reinterpret_cast<const f32x4*>(Vt + d * LF_BLK + (((4 * T + g) ^ (d & 15)) << 2));
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[dt][r], st[T][r], o[dt], 0, 0, 0);
+      }
+    }
+    if (has_next) write(blk + 1);              // the stage every wave finished reading before the last barrier
+    __syncthreads();
+  }
+  if (!active) return;
+  float s = l;
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  const float inv = 1.0f / s;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] *= inv;
+  if (q < N) {
+    if constexpr (OUT == LF_OUT_Q8) {
+      int8_t* op = reinterpret_cast<int8_t*>(out) + ((long)b * N + q) * orow + (long)h * AF_DH + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        *reinterpret_cast<unsigned*>(op + 16 * dt) = affine_i8_pack4<0>(o[dt][0], o[dt][1], o[dt][2], o[dt][3], q_inv, q_zp);
+    } else {
+      float* op = reinterpret_cast<float*>(out) + ((long)b * N + q) * orow + (long)h * AF_DH + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt];
+      if (OUT == LF_OUT_LSE && g == 0) lse[((long)b * H + h) * N + q] = (m + __builtin_amdgcn_logf(s)) * AF_LN2;
+    }
+  }
+}
+
+// delta[b, h, n] = sum_d dO[b, n, h, d] O[b, n, h, d] in fp32: 16 consecutive threads per (token, head), a fixed shuffle tree
+__global__ __launch_bounds__(256) void attn_delta_long_f32_kernel(const float* __restrict__ out, const float* __restrict__ dout,
+                                                                  float* __restrict__ delta, long rows, int N, int H) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;     // = ((b N + n) H + h) 16 + chunk
+  const long rh = idx >> 4;
+  float d = 0.f;
+  if (rh < rows) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(dout + idx * 4), o = *reinterpret_cast<const f32x4*>(out + idx * 4);
+    d = a[0] * o[0] + a[1] * o[1] + a[2] * o[2] + a[3] * o[3];
+  }
+  d += __shfl_xor(d, 1, 64);
+  d += __shfl_xor(d, 2, 64);
+  d += __shfl_xor(d, 4, 64);
+  d += __shfl_xor(d, 8, 64);
+  if (rh < rows && (idx & 15) == 0) {
+    const long bn = rh / H;
+    const int h = (int)(rh % H);
+    const long b = bn / N, n = bn % N;
+    delta[(b * H + h) * N + n] = d;
+  }
+}
+
+__global__ __launch_bounds__(512) void attn_bwd_dkdv_long_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                                     const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                     float* __restrict__ dqkv, int N, int H, int nkb, float scale) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];     // stage s: Q [64][64] | dO [64][64]; then sRow
+  float* const sRow = smem + 2 * LF_STAGE;                         // [stage][lse * log2(e) (+inf past N) | delta (0 past N)][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15, g = lane >> 4;
+  const int bh = blockIdx.x / nkb, kblk = blockIdx.x % nkb;
+  const int b = bh / H, h = bh % H;
+  const long row = 3L * H * AF_DH, orow = (long)H * AF_DH;
+  const float* const qb = qkv + (long)b * N * row + (long)h * AF_DH;
+  const float* const kb = qb + orow;
+  const float* const vb = kb + orow;
+  const float* const dob = dout + (long)b * N * orow + (long)h * AF_DH;
+  const float* const lrow = lse + ((long)b * H + h) * N;
+  const float* const drow = delta + ((long)b * H + h) * N;
+  float* const dkb = dqkv + (long)b * N * row + (long)h * AF_DH + orow;
+  const float sl2 = scale * AF_LOG2E;
+  const int nqb = (N + LF_BLK - 1) / LF_BLK;
+
+  f32x4 qst[2], dst[2];
+  float rst = 0.f;                             // threads 0..63: the block's lse, 64..127: its delta
+  auto issue = [&](int blk) {
+    lf_load_rows(qst, qb, row, blk * LF_BLK, N, tid);
+    lf_load_rows(dst, dob, orow, blk * LF_BLK, N, tid);
+    const int qq = blk * LF_BLK + (tid & 63);
+    if (tid < 64) rst = qq < N ? lrow[qq] * AF_LOG2E : INFINITY;   // log2 units, like the scores below
+    else if (tid < 128) rst = qq < N ? drow[qq] : 0.f;
+  };
+  auto write = [&](int blk) {
+    float* const Qs = smem + (blk & 1) * LF_STAGE;
+    lf_write_rows(Qs, qst, tid);
+    lf_write_rows(Qs + LF_BLK * AF_DH, dst, tid);
+    if (tid < 128) sRow[(blk & 1) * 2 * LF_BLK + tid] = rst;
+  };
+  issue(0);
+  write(0);
+
+  const int k0 = kblk * LF_ROWS + 16 * wave, key = k0 + q16;
+  const bool active = k0 < N;                  // wave-uniform
+  f32x4 kf[4], vf[4];
+  {
+    const long kr = key < N ? key : N - 1;     // clamped: masked below, never stored
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      kf[c] = *reinterpret_cast<const f32x4*>(kb + kr * row + 16 * c + 4 * g);
+      vf[c] = *reinterpret_cast<const f32x4*>(vb + kr * row + 16 * c + 4 * g);
+    }
+  }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  __syncthreads();
+
+  for (int blk = 0; blk < nqb; ++blk) {
+    const bool has_next = blk + 1 < nqb;
+    if (has_next) issue(blk + 1);
+    if (active) {
+      const float* const Qs = smem + (blk & 1) * LF_STAGE;
+      const float* const Ds = Qs + LF_BLK * AF_DH;
+      const float* const sL = sRow + (blk & 1) * 2 * LF_BLK;
+      const float* const sD = sL + LF_BLK;
+#pragma unroll 1
+      for (int T = 0; T < 4; ++T) {            // 16-query tiles of the block
+        f32x4 qa[4], da[4];
+        lf_frag_rows(qa, Qs, T, q16, g);
+        lf_frag_rows(da, Ds, T, q16, g);
+        // sv[r] = S(query 16 T + 4 g + r, key), dp[r] = dP(same)
+        f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) {
+            sv = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[c][kk], kf[c][kk], sv, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_16x16x4f32(da[c][kk], vf[c][kk], dp, 0, 0, 0);
+          }
+        const f32x4 l4 = *reinterpret_cast<const f32x4*>(sL + T * 16 + 4 * g);
+        const f32x4 d4 = *reinterpret_cast<const f32x4*>(sD + T * 16 + 4 * g);
+        f32x4 p, ds;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = key < N ? __builtin_amdgcn_exp2f(sv[r] * sl2 - l4[r]) : 0.f;   // lse = +inf past N: 0
+          p[r] = e;
+          ds[r] = e * (dp[r] - d4[r]) * scale;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            dv[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(p[r], lf_elem(Ds, T, r, dt, q16, g), dv[dt], 0, 0, 0);
+            dk[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[r], lf_elem(Qs, T, r, dt, q16, g), dk[dt], 0, 0, 0);
+          }
+      }
+    }
+    if (has_next) write(blk + 1);
+    __syncthreads();
+  }
+  // dk[dt][r] = dK(key k0 + 4 g + r, feature 16 dt + q16); dV likewise, D floats further on
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int kk = k0 + 4 * g + r;
+    if (kk < N) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        dkb[(long)kk * row + 16 * dt + q16] = dk[dt][r];
+        dkb[(long)kk * row + orow + 16 * dt + q16] = dv[dt][r];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(512) void attn_bwd_dq_long_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                   float* __restrict__ dqkv, int N, int H, int nqb, float scale) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];     // stage s: K [64][64] | V [64][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15, g = lane >> 4;
+  const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
+  const int b = bh / H, h = bh % H;
+  const long row = 3L * H * AF_DH, orow = (long)H * AF_DH;
+  const float* const qb = qkv + (long)b * N * row + (long)h * AF_DH;
+  const float* const kb = qb + orow;
+  const float* const vb = kb + orow;
+  const float* const dob = dout + (long)b * N * orow + (long)h * AF_DH;
+  float* const dqb = dqkv + (long)b * N * row + (long)h * AF_DH;
+  const float sl2 = scale * AF_LOG2E;
+  const int nkb = (N + LF_BLK - 1) / LF_BLK;
+
+  f32x4 kst[2], vst[2];
+  auto issue = [&](int blk) {
+    lf_load_rows(kst, kb, row, blk * LF_BLK, N, tid);
+    lf_load_rows(vst, vb, row, blk * LF_BLK, N, tid);
+  };
+  auto write = [&](int blk) {
+    float* const Ks = smem + (blk & 1) * LF_STAGE;
+    lf_write_rows(Ks, kst, tid);
+    lf_write_rows(Ks + LF_BLK * AF_DH, vst, tid);
+  };
+  issue(0);
+  write(0);
+
+  const int q0 = qblk * LF_ROWS + 16 * wave, q = q0 + q16;
+  const bool active = q0 < N;                  // wave-uniform
+  const long qr = q < N ? q : N - 1;           // clamped: rows >= N are never stored
+  f32x4 qf[4], dof[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    qf[c] = *reinterpret_cast<const f32x4*>(qb + qr * row + 16 * c + 4 * g);
+    dof[c] = *reinterpret_cast<const f32x4*>(dob + qr * orow + 16 * c + 4 * g);
+  }
+  const float l = lse[((long)b * H + h) * N + qr] * AF_LOG2E;
+  const float dl = delta[((long)b * H + h) * N + qr];
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+
+  for (int blk = 0; blk < nkb; ++blk) {
+    const bool has_next = blk + 1 < nkb;
+    if (has_next) issue(blk + 1);
+    if (active) {
+      const float* const Ks = smem + (blk & 1) * LF_STAGE;
+      const float* const Vs = Ks + LF_BLK * AF_DH;
+#pragma unroll 1
+      for (int T = 0; T < 4; ++T) {            // 16-key tiles of the block
+        f32x4 ka[4], va[4];
+        lf_frag_rows(ka, Ks, T, q16, g);
+        lf_frag_rows(va, Vs, T, q16, g);
+        // st[r] = S(query q, key 64 blk + 16 T + 4 g + r), dp[r] = dP(same)
+        f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) {
+            st = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[c][kk], qf[c][kk], st, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][kk], dof[c][kk], dp, 0, 0, 0);
+          }
+        f32x4 ds;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = blk * LF_BLK + T * 16 + 4 * g + r;
+          const float p = key < N ? __builtin_amdgcn_exp2f(st[r] * sl2 - l) : 0.f;
+          ds[r] = p * (dp[r] - dl) * scale;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt)
+            dq[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[r], lf_elem(Ks, T, r, dt, q16, g), dq[dt], 0, 0, 0);
+      }
+    }
+    if (has_next) write(blk + 1);
+    __syncthreads();
+  }
+  // dq[dt][r] = dQ(query q0 + 4 g + r, feature 16 dt + q16)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qq = q0 + 4 * g + r;
+    if (qq < N) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) dqb[(long)qq * row + 16 * dt + q16] = dq[dt][r];
+    }
+  }
+}
+
+template <typename K>
+int lf_set_smem(K kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess
+             ? 0 : -1;
+}
+
+template <int OUT>
+int launch_attn_fwd_long_f32(const float* qkv, void* out, float* lse, int B, int N, int H, float scale, float q_inv,
+                             float q_zp, hipStream_t s) {
+  constexpr int lds = 2 * LF_STAGE * (int)sizeof(float);
+  if (MV_ONCE_PER_DEVICE(lf_set_smem(attn_fwd_long_f32_kernel<OUT>, lds))) return MV_ERR_LAUNCH;
+  const long nqb = (N + LF_ROWS - 1) / LF_ROWS;
+  attn_fwd_long_f32_kernel<OUT><<<(unsigned)(nqb * B * H), 512, lds, s>>>(qkv, out, lse, N, H, (int)nqb, scale * AF_LOG2E,
+                                                                           q_inv, q_zp);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
 }  // namespace
 
 extern "C" int mv_attention_fwd_f32(const float* qkv, float* out, int B, int N, int H, float scale, mv_stream_t stream) {
@@ -502,4 +944,49 @@ extern "C" int mv_attention_bwd_f32(const float* qkv, const float* out, const fl
   hipStream_t s = (hipStream_t)stream;
   return N <= 208 ? launch_attn_bwd_f32<13>(qkv, out, dout, lse, dqkv, B, N, H, scale, s)
                   : launch_attn_bwd_f32<17>(qkv, out, dout, lse, dqkv, B, N, H, scale, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// any 1 <= N <= 8192: the key-tiled kernels (ops.attention_fwd_f32 / _f32_lse / _f32_q8 / attention_bwd_f32_fused route N > 272 here)
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int mv_attention_fwd_long_f32(const float* qkv, float* out, float* lse, int B, int N, int H, float scale,
+                                         mv_stream_t stream) {
+  MV_REQUIRE(B >= 0 && N > 0 && H > 0, MV_ERR_SHAPE);
+  MV_REQUIRE(N <= LF_MAX_N, MV_ERR_UNSUPPORTED);
+  MV_REQUIRE((long)(N + LF_ROWS - 1) / LF_ROWS * B * H < (1L << 31), MV_ERR_SHAPE);
+  MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(out), MV_ERR_ALIGN);
+  if (B == 0) return MV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return lse ? launch_attn_fwd_long_f32<LF_OUT_LSE>(qkv, out, lse, B, N, H, scale, 0.f, 0.f, s)
+             : launch_attn_fwd_long_f32<LF_OUT_PLAIN>(qkv, out, nullptr, B, N, H, scale, 0.f, 0.f, s);
+}
+
+extern "C" int mv_attention_fwd_long_f32_q8(const float* qkv, void* codes, int B, int N, int H, float scale, float q_scale,
+                                            int q_zero_point, mv_stream_t stream) {
+  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && q_scale > 0.f, MV_ERR_SHAPE);
+  MV_REQUIRE(N <= LF_MAX_N && q_zero_point >= 0 && q_zero_point <= 255, MV_ERR_UNSUPPORTED);
+  MV_REQUIRE((long)(N + LF_ROWS - 1) / LF_ROWS * B * H < (1L << 31), MV_ERR_SHAPE);
+  MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(codes), MV_ERR_ALIGN);
+  if (B == 0) return MV_OK;
+  return launch_attn_fwd_long_f32<LF_OUT_Q8>(qkv, codes, nullptr, B, N, H, scale, 1.0f / q_scale, (float)q_zero_point,
+                                             (hipStream_t)stream);
+}
+
+extern "C" int mv_attention_bwd_long_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* delta_ws,
+                                         float* dqkv, int B, int N, int H, float scale, mv_stream_t stream) {
+  MV_REQUIRE(B >= 0 && N > 0 && H > 0, MV_ERR_SHAPE);
+  MV_REQUIRE(N <= LF_MAX_N, MV_ERR_UNSUPPORTED);
+  const long nb = (N + LF_ROWS - 1) / LF_ROWS, rows = (long)B * N * H;
+  MV_REQUIRE(nb * B * H < (1L << 31) && (rows * 16 + 255) / 256 < (1L << 31), MV_ERR_SHAPE);
+  MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(out) && mv_aligned16(dout) && mv_aligned16(dqkv) && lse && delta_ws, MV_ERR_ALIGN);
+  if (B == 0) return MV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  constexpr int lds_dkdv = (2 * LF_STAGE + 4 * LF_BLK) * (int)sizeof(float), lds_dq = 2 * LF_STAGE * (int)sizeof(float);
+  if (MV_ONCE_PER_DEVICE(lf_set_smem(attn_bwd_dkdv_long_f32_kernel, lds_dkdv) | lf_set_smem(attn_bwd_dq_long_f32_kernel, lds_dq)))
+    return MV_ERR_LAUNCH;
+  attn_delta_long_f32_kernel<<<(unsigned)((rows * 16 + 255) / 256), 256, 0, s>>>(out, dout, delta_ws, rows, N, H);
+  attn_bwd_dkdv_long_f32_kernel<<<(unsigned)(nb * B * H), 512, lds_dkdv, s>>>(qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
+  attn_bwd_dq_long_f32_kernel<<<(unsigned)(nb * B * H), 512, lds_dq, s>>>(qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
 }

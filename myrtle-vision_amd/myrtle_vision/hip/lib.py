@@ -58,6 +58,9 @@ SIGNATURES = {
     "mv_attention_bwd_f16": ("pppppp" "ip" "iii" "f" "p", _I),
     "mv_attention_fwd_long_f16": ("ppp" "iii" "f" "p", _I),
     "mv_attention_bwd_long_f16": ("pppppp" "ipp" "iii" "f" "p", _I),
+    "mv_attention_fwd_long_f32": ("ppp" "iii" "f" "p", _I),
+    "mv_attention_fwd_long_f32_q8": ("pp" "iii" "f" "f" "i" "p", _I),
+    "mv_attention_bwd_long_f32": ("ppppp" "p" "iii" "f" "p", _I),
     "mv_softmax_fwd": ("pp" "li" "f" "p", _I),
     "mv_softmax_bwd": ("ppp" "li" "f" "p", _I),
     "mv_patchify": ("ppi" "iiiii" "p", _I),

@@ -13,6 +13,8 @@ inside BASELINE's 1e-3 end to end; ``"bf16x3h"`` = bf16x3 with the attention cor
 templated on the element type, fp32 sums / softmax / outputs): logits still 7x inside 1e-3 and every arg-max exact, gradients to
 1.6e-3 (twelve layers of 2^-12 roundings of q and k under the exponential), 20 % faster than bf16x3.  The half core covers any
 sequence up to 8 192 tokens: the whole-head kernels up to 288, the key-tiled ones above (384^2 fine-tuning, 512^2 segmentation).
+The exact-fp32 attention core of ``"fp32"`` and ``"bf16x3"`` (and of the converted int8 model) does the same: the whole-head
+f32-MFMA kernels up to 272 tokens, the key-tiled ones above, so no length materialises the [B, H, N, N] probabilities.
 """
 import ctypes
 import os
@@ -822,8 +824,9 @@ def colsum(x, rows, cols, ld, out):
 ATTN_SHORT_MAX_N = 320      # the whole-head kernels (mv_attention_fwd / _bwd): K and V of a head in LDS
 ATTN_LONG_MAX_N = 8192      # the key-tiled kernels (mv_attention_fwd_long / _bwd_long, and their half forms _long_f16)
 ATTN_F16_SHORT_MAX_N = 288  # the whole-head half kernels (mv_attention_fwd_f16 / _bwd_f16)
-# A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320 and the half attention of bf16x3h with
-# N > 288 back to the materialised fp32 path
+ATTN_F32_SHORT_MAX_N = 272  # the whole-head fp32 kernels (mv_attention_fwd_f32 / _f32_lse / _f32_q8 / _bwd_f32)
+# A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320, the half attention of bf16x3h with
+# N > 288 and the fp32 attention of fp32 / bf16x3 with N > 272 back to the materialised fp32 path
 ATTN_LONG = True
 
 
@@ -874,7 +877,10 @@ def attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=None):
 
 
 def attention_f32_fused_supported(qkv_dtype, N, dim_head):
-    return qkv_dtype == torch.float32 and dim_head == 64 and N <= 272
+    """The exact-fp32 attention core (precisions "fp32" and "bf16x3", the converted int8 model): fp32 q/k/v, N <= 8192 (the
+    whole-head kernels up to 272 tokens, the key-tiled ones above; 272 with ``ATTN_LONG`` off)."""
+    cap = ATTN_LONG_MAX_N if ATTN_LONG else ATTN_F32_SHORT_MAX_N
+    return qkv_dtype == torch.float32 and dim_head == 64 and N <= cap
 
 
 def attention_f16_supported(qkv_dtype, N, dim_head):
@@ -955,7 +961,10 @@ def attention_bwd_long_f16(qkv16, out, dout, lse, B, N, H, scale, split=False, c
 
 
 def attention_fwd_f32(qkv, B, N, H, scale):
-    """Exact fp32 attention core, forward only (no probabilities kept): qkv fp32 [B, N, 3*H*64] -> out fp32 [B, N, H*64]."""
+    """Exact fp32 attention core, forward only (no probabilities kept): qkv fp32 [B, N, 3*H*64] -> out fp32 [B, N, H*64].
+    N > 272 takes the key-tiled kernel."""
+    if N > ATTN_F32_SHORT_MAX_N:
+        return attention_fwd_long_f32(qkv, B, N, H, scale, lse=False)
     require_cuda(qkv)
     out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv.device)
     check(lib().mv_attention_fwd_f32(_p(qkv), _p(out), B, N, H, scale, _s()), "attention_fwd_f32", B=B, N=N, H=H)
@@ -963,7 +972,10 @@ def attention_fwd_f32(qkv, B, N, H, scale):
 
 
 def attention_fwd_f32_lse(qkv, B, N, H, scale):
-    """fp32 attention core for training: -> (out fp32 [B, N, H*64], lse fp32 [B, H, N]); no probabilities are kept."""
+    """fp32 attention core for training: -> (out fp32 [B, N, H*64], lse fp32 [B, H, N]); no probabilities are kept.
+    N > 272 takes the key-tiled kernel."""
+    if N > ATTN_F32_SHORT_MAX_N:
+        return attention_fwd_long_f32(qkv, B, N, H, scale)
     require_cuda(qkv)
     out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
@@ -973,10 +985,34 @@ def attention_fwd_f32_lse(qkv, B, N, H, scale):
 
 
 def attention_bwd_f32_fused(qkv, out, dout, lse, B, N, H, scale):
-    """-> dqkv fp32 (qkv's layout) from the saved output and log-sum-exp."""
+    """-> dqkv fp32 (qkv's layout) from the saved output and log-sum-exp.  N > 272 takes the key-tiled kernels."""
+    if N > ATTN_F32_SHORT_MAX_N:
+        return attention_bwd_long_f32(qkv, out, dout, lse, B, N, H, scale)
     dqkv = torch.empty_like(qkv)
     check(lib().mv_attention_bwd_f32(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), B, N, H, scale, _s()),
           "attention_bwd_f32", B=B, N=N, H=H)
+    return dqkv
+
+
+def attention_fwd_long_f32(qkv, B, N, H, scale, lse=True):
+    """The key-tiled exact-fp32 forward (any N <= 8192): -> (out, lse) as ``attention_fwd_f32_lse``, or out alone (``lse=False``,
+    as ``attention_fwd_f32``)."""
+    require_cuda(qkv)
+    out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv.device)
+    lse_t = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device) if lse else None
+    check(lib().mv_attention_fwd_long_f32(_p(qkv), _p(out), _p(lse_t), B, N, H, scale, _s()), "attention_fwd_long_f32",
+          B=B, N=N, H=H)
+    return (out, lse_t) if lse else out
+
+
+def attention_bwd_long_f32(qkv, out, dout, lse, B, N, H, scale):
+    """The key-tiled exact-fp32 backward (any N <= 8192): as ``attention_bwd_f32_fused``; the delta workspace is a torch
+    allocation (graph capture)."""
+    require_cuda(qkv, out, dout, lse)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    check(lib().mv_attention_bwd_long_f32(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, N, H, scale, _s()),
+          "attention_bwd_long_f32", B=B, N=N, H=H)
     return dqkv
 
 
@@ -1246,11 +1282,23 @@ def layernorm_q8(x, ldx, rows, dim, gamma, beta, eps, scale, zero_point):
 
 
 def attention_fwd_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point):
-    """Exact fp32 attention core whose output goes straight into a quint8 quantiser: -> int8 codes [B, N, H*64]."""
+    """Exact fp32 attention core whose output goes straight into a quint8 quantiser: -> int8 codes [B, N, H*64].  N > 272 takes
+    the key-tiled kernel."""
+    if N > ATTN_F32_SHORT_MAX_N:
+        return attention_fwd_long_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point)
     require_cuda(qkv)
     codes = torch.empty(B, N, H * 64, dtype=torch.int8, device=qkv.device)
     check(lib().mv_attention_fwd_f32_q8(_p(qkv), _p(codes), B, N, H, scale, float(q_scale), int(q_zero_point), _s()),
           "attention_fwd_f32_q8", B=B, N=N, H=H)
+    return codes
+
+
+def attention_fwd_long_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point):
+    """The key-tiled form of ``attention_fwd_f32_q8`` (any N <= 8192)."""
+    require_cuda(qkv)
+    codes = torch.empty(B, N, H * 64, dtype=torch.int8, device=qkv.device)
+    check(lib().mv_attention_fwd_long_f32_q8(_p(qkv), _p(codes), B, N, H, scale, float(q_scale), int(q_zero_point), _s()),
+          "attention_fwd_long_f32_q8", B=B, N=N, H=H)
     return codes
 
 

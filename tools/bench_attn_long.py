@@ -10,8 +10,11 @@ kernels (ops.attention_fwd_long_f16 / _bwd_long_f16, the backward with its dO pr
 the prep pass alone is timed as "prep")
 against the materialised fp32 path of functional._AttnBlock's fp32 branch (no casts), and at N = 257 against mv_attention_fwd_f16 /
 _bwd_f16.
+``--f32``: the same for the exact-fp32 core of precisions "fp32" / "bf16x3": the key-tiled f32 kernels (ops.attention_fwd_long_f32
+with its lse / _bwd_long_f32, the backward with its delta pass) against the same materialised fp32 path, and at N = 257 against the
+whole-head fp32 kernels (mv_attention_fwd_f32_lse / mv_attention_bwd_f32).
 
-    python tools/bench_attn_long.py [--half] [--out FILE]      (prints a table; FILE gets the same table and one JSON line per case)"""
+    python tools/bench_attn_long.py [--half | --f32] [--out FILE]      (prints a table; FILE gets the same table and one JSON line per case)"""
 import argparse
 import json
 import os
@@ -92,18 +95,40 @@ def half_arms(B, N, gen):
     return arms
 
 
+def f32_arms(B, N, gen):
+    """The fp32 / bf16x3 arms: fp32 q/k/v and dout throughout."""
+    q32 = torch.randn(B, N, 3 * H * 64, device="cuda", generator=gen) * 0.8
+    dout = torch.randn(B, N, H * 64, device="cuda", generator=gen)
+    out, lse = ops.attention_fwd_long_f32(q32, B, N, H, SCALE)
+    arms = {
+        "long_fwd": lambda: ops.attention_fwd_long_f32(q32, B, N, H, SCALE),
+        "long_bwd": lambda: ops.attention_bwd_long_f32(q32, out, dout, lse, B, N, H, SCALE),
+    }
+    if N <= ops.ATTN_F32_SHORT_MAX_N:
+        sout, slse = ops.attention_fwd_f32_lse(q32, B, N, H, SCALE)
+        arms["short_fwd"] = lambda: ops.attention_fwd_f32_lse(q32, B, N, H, SCALE)
+        arms["short_bwd"] = lambda: ops.attention_bwd_f32_fused(q32, sout, dout, slse, B, N, H, SCALE)
+    else:
+        probs = ops.attention_probs_fp32(q32, B, N, H, 64, SCALE)
+        arms["mat_fwd"] = lambda: ops.attention_pv_fp32(ops.attention_probs_fp32(q32, B, N, H, 64, SCALE), q32, B, N, H, 64)
+        arms["mat_bwd"] = lambda: ops.attention_bwd_fp32(probs, q32, dout, B, N, H, 64, SCALE)
+    return arms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--half", action="store_true", help="the half-operand core of bf16x3h instead of the bf16 one")
+    kind = ap.add_mutually_exclusive_group()
+    kind.add_argument("--half", action="store_true", help="the half-operand core of bf16x3h instead of the bf16 one")
+    kind.add_argument("--f32", action="store_true", help="the exact-fp32 core of fp32 / bf16x3 instead of the bf16 one")
     args = ap.parse_args()
     lines, rows = [], []
     dev = torch.cuda.get_device_name(0)
-    short_cap = ops.ATTN_F16_SHORT_MAX_N if args.half else ops.ATTN_SHORT_MAX_N
+    short_cap = ops.ATTN_F16_SHORT_MAX_N if args.half else ops.ATTN_F32_SHORT_MAX_N if args.f32 else ops.ATTN_SHORT_MAX_N
     for B, N in CASES:
         gen = torch.Generator(device="cuda").manual_seed(N)
         iters = max(3, min(50, int(2e12 / (10.0 * B * H * N * N * 64) * 20)))
-        arms = half_arms(B, N, gen) if args.half else bf16_arms(B, N, gen)
+        arms = half_arms(B, N, gen) if args.half else f32_arms(B, N, gen) if args.f32 else bf16_arms(B, N, gen)
         best = {k: 1e30 for k in arms}
         for _ in range(ROUNDS):
             for k, fn in arms.items():
@@ -113,6 +138,8 @@ def main():
         rec = {"B": B, "N": N, "H": H, "device": dev, "iters": iters, "rounds": ROUNDS}
         if args.half:
             rec["core"] = "half (bf16x3h)"
+        elif args.f32:
+            rec["core"] = "fp32 (fp32, bf16x3)"
         for k, us in best.items():
             rec[k + "_us"] = round(us, 1)
             if k == "prep":
@@ -138,6 +165,11 @@ def main():
                         "# core of bf16x3h (long bwd includes the dO prep pass and the column sums)\n"
                         "# vs: mat = materialised fp32 path (functional._AttnBlock's fp32 branch above 288 tokens before), short = the\n"
                         "# whole-head half kernels\n")
+            elif args.f32:
+                f.write(f"# tools/bench_attn_long.py --f32 on {dev}, ViT-B heads (H = 12), best of {ROUNDS} alternating rounds: the exact-fp32\n"
+                        "# core of fp32 / bf16x3 on the f32 matrix cores (long bwd includes the delta pass)\n"
+                        "# vs: mat = materialised fp32 path (functional._AttnBlock above 272 tokens before), short = the whole-head fp32\n"
+                        "# kernels\n")
             else:
                 f.write(f"# tools/bench_attn_long.py on {dev}, ViT-B heads (H = 12), best of {ROUNDS} alternating rounds\n"
                         "# vs: mat = materialised fp32 path (functional._AttnBlock above 320 tokens before), short = the whole-head kernels\n")

@@ -3,9 +3,10 @@
 default) against the materialised fp32 attention the step took before (False), alternating in blocks of STEPS steps for ROUNDS
 rounds in one process.  Per arm: ms/step (mean, std, min over blocks), img/s and torch.cuda.max_memory_allocated over the arm's
 blocks.  PRECISION=bf16x3h (or any other ViT precision; default bf16) runs that precision's step instead: for bf16x3h the arms
-are the key-tiled half kernels against the materialised fp32 path; the lines then carry a "precision" field.
+are the key-tiled half kernels against the materialised fp32 path, for fp32 / bf16x3 the key-tiled fp32 kernels against it; the
+lines then carry a "precision" field.
 
-    ROUNDS=4 STEPS=5 [PRECISION=bf16x3h] python tools/bench_long_step.py [--out FILE]"""
+    ROUNDS=4 STEPS=5 [PRECISION=bf16x3h|fp32|bf16x3] python tools/bench_long_step.py [--out FILE]"""
 import argparse
 import json
 import os
