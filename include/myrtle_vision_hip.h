@@ -165,6 +165,19 @@ int mv_attention_bwd(const void* qkv, const void* out, const void* dout, const f
 int mv_attention_fwd_long(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, mv_stream_t stream);
 int mv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, float* delta_ws, void* dqkv,
                           float* colsum, int B, int N, int H, float scale, mv_stream_t stream);
+/* The bf16 attention core for head widths other than 64 (Attention.forward vit.py:85-99; dim_head is a constructor argument of the
+ * reference's ViT / Attention and only heads * dim_head is fixed by the model width): dim_head 32 or 128, any 1 <= N <= 8192.
+ * Key-tiled kernels like mv_attention_fwd_long / _bwd_long with the same rounding points (P and dS rounded to bf16 before their
+ * products, fp32 softmax and accumulation, outputs rounded once) and no [N, N] tensor.  qkv: bf16 [B, N, 3, H, dim_head];
+ * out / dout: bf16 [B, N, H * dim_head]; lse: fp32 [B, H, N], natural-log units; dqkv as qkv; every bf16 tensor 16-byte aligned.
+ * delta_ws: caller-provided fp32 workspace of B * H * N floats (receives rowsum(dout * out)).  colsum (nullable): fp32
+ * [B, 3 * H * dim_head], per-image column sums of the bf16 dqkv rows in a fixed order (to_qkv's bias-gradient partials).
+ * Deterministic: no atomics, every output has one owner.  N outside 1 .. 8192: MV_ERR_SHAPE; a misaligned pointer: MV_ERR_ALIGN;
+ * any other dim_head: MV_ERR_UNSUPPORTED (64: mv_attention_fwd / _fwd_long) -- nothing is launched in these cases. */
+int mv_attention_fwd_dh(const void* qkv, void* out, float* lse, int B, int N, int H, int dim_head, float scale,
+                        mv_stream_t stream);
+int mv_attention_bwd_dh(const void* qkv, const void* out, const void* dout, const float* lse, float* delta_ws, void* dqkv,
+                        float* colsum, int B, int N, int H, int dim_head, float scale, mv_stream_t stream);
 /* The attention core of precision "bf16x3" (vit.py:87-96 between fp32 tensors): the fused kernels above on IEEE-half operands with
  * fp32 accumulation, softmax and OUTPUTS; N <= 288 (longer: mv_attention_fwd_long_f16 below; N <= 208: the 13-key-tile kernels; above: the two-pass kernels of the 257-token case).  qkv16: half [B, N, 3, H, 64] (mv_cast to MV_F16 of the fp32 to_qkv output);
  * out / lse as mv_attention_fwd but out is fp32.  Backward: mv_attention_bwd_prep_f16 turns the fp32 dout [B, N, H*64] into half

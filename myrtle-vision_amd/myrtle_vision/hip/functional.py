@@ -296,6 +296,31 @@ class _AttentionFused(Function):
         return ops.attention_bwd(qkv, out, dout, lse, B, N, ctx.heads, ctx.scale), None, None
 
 
+class _AttentionFusedDh(Function):
+    """``_AttentionFused`` for the head widths of ``ops.ATTN_DH_WIDTHS`` (32, 128).  qkv bf16 [B, N, 3*H*dh] -> [B, N, H*dh]."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, qkv, heads, scale):
+        B, N, three_d = qkv.shape
+        qkv = _c(qkv)
+        dh = three_d // (3 * heads)
+        out, lse = ops.attention_fwd_dh(qkv, B, N, heads, dh, scale)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads, ctx.dh, ctx.scale = heads, dh, scale
+        return out
+
+    @staticmethod
+    @_scoped
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        B, N, _ = qkv.shape
+        dout = _c(dout)
+        if dout.dtype != torch.bfloat16:
+            dout = ops.cast(dout, torch.bfloat16)
+        return ops.attention_bwd_dh(qkv, out, dout, lse, B, N, ctx.heads, ctx.dh, ctx.scale), None, None
+
+
 class _AttentionProbs(Function):
     """Materialised fp32 path, part 1: probs = softmax(q k^T * scale)  [B, H, N, N] (vit.py:92-93)."""
 
@@ -390,11 +415,13 @@ def attention_core(qkv, heads, scale, probs_hook=None):
 
     ``probs_hook`` (callable or None) is the reference's ``attn_output`` Identity (vit.py:80-82,94): when it has
     forward hooks the probabilities are materialised (fp32) and passed through it; otherwise bf16 inputs take the
-    fused kernel."""
+    fused kernels (head widths 64, 32 and 128)."""
     B, N, three_d = qkv.shape
     dh = three_d // (3 * heads)
     if probs_hook is None and ops.attention_fused_supported(qkv.dtype, N, dh):
         return _AttentionFused.apply(qkv, heads, scale)
+    if probs_hook is None and ops.attention_dh_supported(qkv.dtype, N, dh):
+        return _AttentionFusedDh.apply(qkv, heads, scale)
     if (probs_hook is None and ops.attention_f32_fused_supported(qkv.dtype, N, dh)
             and not (torch.is_grad_enabled() and qkv.requires_grad)):
         # no gradient wanted (converted int8 model, fp32 evaluation): exact fp32 arithmetic without the probabilities
@@ -580,6 +607,9 @@ class _AttnBlock(Function):
         if ops.attention_fused_supported(adt, T, dh):
             o, lse = ops.attention_fwd(qkv, B, T, heads, scale)
             probs = None
+        elif ops.attention_dh_supported(adt, T, dh):             # 32- and 128-wide heads: kernels of their own
+            o, lse = ops.attention_fwd_dh(qkv, B, T, heads, dh, scale)
+            probs = None
         elif ops.attention_f32_fused_supported(adt, T, dh) and not any(ctx.needs_input_grad):
             # fp32 evaluation: nothing will run backward, so the probabilities need not exist
             o, lse, probs = ops.attention_fwd_f32(qkv, B, T, heads, scale), None, None
@@ -653,7 +683,11 @@ class _AttnBlock(Function):
         if fused:
             # the kernel also leaves per-image column sums of dqkv: to_qkv's bias gradient without another pass over dqkv
             part = torch.empty(B, inner3, dtype=torch.float32, device=x.device)
-            dqkv = ops.attention_bwd(qkv, o, do, lse_or_probs, B, T, heads, scale, colsum=part)
+            dh = inner // heads
+            if dh == 64:
+                dqkv = ops.attention_bwd(qkv, o, do, lse_or_probs, B, T, heads, scale, colsum=part)
+            else:
+                dqkv = ops.attention_bwd_dh(qkv, o, do, lse_or_probs, B, T, heads, dh, scale, colsum=part)
             dbqkv = ops.colsum(part, B, inner3, inner3, ops.grad_out(bqkv, (inner3,), x.device))
         elif getattr(ctx, "fused32", False):
             dqkv = ops.attention_bwd_f32_fused(qkv, o, do, lse_or_probs, B, T, heads, scale)

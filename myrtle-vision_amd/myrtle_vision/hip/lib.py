@@ -52,6 +52,8 @@ SIGNATURES = {
     "mv_attention_bwd": ("pppppp" "iii" "f" "p", _I),
     "mv_attention_fwd_long": ("ppp" "iii" "f" "p", _I),
     "mv_attention_bwd_long": ("ppppppp" "iii" "f" "p", _I),
+    "mv_attention_fwd_dh": ("ppp" "iiii" "f" "p", _I),
+    "mv_attention_bwd_dh": ("ppppppp" "iiii" "f" "p", _I),
     "mv_attention_fwd_f32": ("pp" "iii" "f" "p", _I),
     "mv_attention_fwd_f16": ("ppp" "iii" "f" "p", _I),
     "mv_attention_bwd_prep_f16": ("ppppp" "iii" "p", _I),

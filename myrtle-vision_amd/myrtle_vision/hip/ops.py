@@ -826,7 +826,8 @@ ATTN_LONG_MAX_N = 8192      # the key-tiled kernels (mv_attention_fwd_long / _bw
 ATTN_F16_SHORT_MAX_N = 288  # the whole-head half kernels (mv_attention_fwd_f16 / _bwd_f16)
 ATTN_F32_SHORT_MAX_N = 272  # the whole-head fp32 kernels (mv_attention_fwd_f32 / _f32_lse / _f32_q8 / _bwd_f32)
 # A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320, the half attention of bf16x3h with
-# N > 288 and the fp32 attention of fp32 / bf16x3 with N > 272 back to the materialised fp32 path
+# N > 288, the fp32 attention of fp32 / bf16x3 with N > 272 and bf16 attention with 32- or 128-wide heads (any N) back to the
+# materialised fp32 path
 ATTN_LONG = True
 
 
@@ -854,6 +855,36 @@ def attention_bwd(qkv, out, dout, lse, B, N, H, scale, colsum=None):
     dqkv = torch.empty_like(qkv)
     check(lib().mv_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(colsum), B, N, H, scale, _s()),
           "attention_bwd", B=B, N=N, H=H)
+    return dqkv
+
+
+ATTN_DH_WIDTHS = (32, 128)  # head widths other than 64 with fused bf16 kernels (mv_attention_fwd_dh / _bwd_dh), any N <= 8192
+
+
+def attention_dh_supported(qkv_dtype, N, dim_head):
+    """The key-tiled bf16 kernels for the head widths in ``ATTN_DH_WIDTHS`` (64 has kernels of its own: ``attention_fused_supported``):
+    bf16 q/k/v, N <= 8192.  They are key-tiled kernels, so ``ATTN_LONG`` off sends these widths back to the materialised path too."""
+    return ATTN_LONG and qkv_dtype == torch.bfloat16 and dim_head in ATTN_DH_WIDTHS and N <= ATTN_LONG_MAX_N
+
+
+def attention_fwd_dh(qkv, B, N, H, dim_head, scale):
+    """qkv bf16 [B, N, 3*H*dim_head] -> (out bf16 [B, N, H*dim_head], lse fp32 [B, H, N]); dim_head 32 or 128, any N <= 8192."""
+    require_cuda(qkv)
+    out = torch.empty(B, N, H * dim_head, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    check(lib().mv_attention_fwd_dh(_p(qkv), _p(out), _p(lse), B, N, H, dim_head, scale, _s()), "attention_fwd_dh", B=B, N=N, H=H,
+          dim_head=dim_head)
+    return out, lse
+
+
+def attention_bwd_dh(qkv, out, dout, lse, B, N, H, dim_head, scale, colsum=None):
+    """-> dqkv, as ``attention_bwd_long`` for dim_head 32 or 128 (``colsum``: optional fp32 [B, 3*H*dim_head]); the delta workspace
+    is a torch allocation (graph capture)."""
+    require_cuda(qkv, out, dout, lse)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    check(lib().mv_attention_bwd_dh(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(colsum), B, N, H, dim_head, scale,
+                                    _s()), "attention_bwd_dh", B=B, N=N, H=H, dim_head=dim_head)
     return dqkv
 
 

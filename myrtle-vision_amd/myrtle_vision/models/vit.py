@@ -218,6 +218,10 @@ class FeedForward(nn.Module):
 
 # ---- reference vit.py:59-99 ---------------------------------------------------------------------------------
 class Attention(nn.Module):
+    """``dim_head``: with ``precision="bf16"`` the attention core is fused for 64-wide heads (whole-head kernels up to 320 tokens,
+    key-tiled ones above) and for 32- and 128-wide heads (key-tiled kernels, any length up to 8 192); other widths, and 32 / 128
+    in the fp32-qkv precisions, run on the materialised fp32 path."""
+
     def __init__(self, dim: int, heads: int = 8, dim_head: int = 64, dropout: float = 0.0):
         super().__init__()
         inner_dim = dim_head * heads

@@ -33,6 +33,11 @@ def sw256(row, ch):          # 256-byte rows (128 bf16): image used by gemm TN t
     return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)))
 
 
+def sw_dh(dh, row, ch):      # attention_dh.hip: [64][dh] bf16 blocks, rows of 2 dh bytes (dh = 32: 64 B, dh = 128: 256 B)
+    f = ((row >> 2) & 1) << 1 if dh == 32 else (row & 7) << 1
+    return 2 * dh * row + 16 * (ch ^ f)
+
+
 def main():
     worst = 0
     # 1. MFMA 16x16x32 A/B fragment as ds_read_b128 from 128-B rows: lane l -> row base+(l&15), chunk 4ks+(l>>4)
@@ -80,6 +85,23 @@ def main():
         a = [sw128((l & 15), (8 * (l >> 4) + 32 * j) // 16) + (8 * (l >> 4) + 32 * j) % 16 for l in range(64)]
         cy = cycles(a, 8, HALVES, 64)
         print(f"b64 row read (k-permuted) j={j}: {cy} cycles (ideal 2)")
+    # 6. "dh" cases: attention_dh.hip's images for 32- and 128-wide heads.  Row fragments: lane -> row base+(l&15), chunk 4ks+(l>>4);
+    #    transposed fragments in the accumulator's k order: rows base+4g+q (and +16), chunk 2dt+(p>>1), + 8 (p&1)
+    for dh in (32, 128):
+        wr = wt = 0
+        for base in (0, 16, 32, 48):
+            for ks in range(dh // 32):
+                a = [sw_dh(dh, base + (l & 15), 4 * ks + (l >> 4)) for l in range(64)]
+                wr = max(wr, cycles(a, 16, B128_GROUPS, 64))
+            for dt in range(dh // 16):
+                a = []
+                for l in range(64):
+                    g, i = l >> 4, l & 15
+                    q, p = i >> 2, i & 3
+                    a.append(sw_dh(dh, base + 4 * g + q, 2 * dt + (p >> 1)) + 8 * (p & 1))
+                wt = max(wt, cycles(a, 8, HALVES, 64))
+        worst = max(worst, wr - 4, wt - 2)
+        print(f"dh = {dh:3d}: b128 row read {wr} cycles (ideal 4), tr read {wt} cycles (ideal 2), over every tile base, k-step and d-tile")
     print("worst excess:", worst)
 
 
