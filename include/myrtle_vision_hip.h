@@ -424,6 +424,54 @@ int mv_seg_ce_fwd(const float* small, const int64_t* labels, float* lse, uint8_t
 int mv_seg_ce_bwd(const float* small, const int64_t* labels, const float* lse, const float* stats, void* dsmall,
                   int ds_dtype, int ld_ds, float grad_scale, int B, int C, int h, int w, int H, int W, mv_stream_t stream);
 
+/* ---- YOLOS detection tail (csrc/detection.hip).  Everything is fp32 in every precision; Q = num_det_tokens queries per image,
+ * C1 = num_classes + 1 (the last class is "no object"), boxes are (cx, cy, w, h) in [0, 1]. ----
+ * decoder: vit.py:376-396 DetectionDecoder.forward -- x[:, -Q:, :] -> class_embed, bbox_embed + sigmoid -- in one pass over the
+ * gathered rows.  x: [B, T, D] (only its last Q rows per image are read); logits [B, Q, C1]; boxes [B, Q, 4] (after the sigmoid).
+ * bwd: dlogits / dboxes (either may be NULL = zero) -> dx (NULL, or [B, T, D] whose last Q rows per image are WRITTEN, the caller
+ * zero-fills the rest), dw_cls [C1, D], db_cls [C1], dw_box [4, D], db_box [4]; the sigmoid derivative is applied in-kernel from
+ * the saved boxes.  Deterministic: row slabs into the workspace, then a fixed-order sum. */
+int mv_det_heads_fwd(const float* x, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
+                     float* logits, float* boxes, int B, int T, int Q, int D, int C1, mv_stream_t stream);
+size_t mv_det_heads_bwd_workspace_bytes(int B, int Q, int D, int C1);
+int mv_det_heads_bwd(const float* x, const float* w_cls, const float* w_box, const float* boxes, const float* dlogits,
+                     const float* dboxes, float* dx, float* dw_cls, float* db_cls, float* dw_box, float* db_box,
+                     void* workspace, size_t workspace_bytes, int B, int T, int Q, int D, int C1, mv_stream_t stream);
+/* sequence assembly YOLOS intends (vit.py:285-302 with its "detection" branch taken, which the reference never does):
+ * out [B, T0 + Q, D] = cat(x [B, T0, D], det [Q, D] + pos [Q, D]).  bwd: dx [B, T0, D] = dout[:, :T0], ddet = dpos [Q, D] = the
+ * sum over the batch of dout[:, T0:], in batch order (no float atomics). */
+int mv_det_append_fwd(const float* x, const float* det, const float* pos, float* out, int B, int T0, int Q, int D,
+                      mv_stream_t stream);
+int mv_det_append_bwd(const float* dout, float* dx, float* ddet, float* dpos, int B, int T0, int Q, int D,
+                      mv_stream_t stream);
+/* matching cost, matcher.py:58-82: only the per-image blocks of the reference's [B*Q, sum T] matrix.  labels int64 [sum T],
+ * tboxes [sum T, 4], toff int32 [B + 1] (prefix sums of the target counts).  out: packed fp32, the [Q, T_b] block of image b
+ * (row-major) starts at Q * toff[b]:  cost_bbox * L1 - cost_class * softmax(logits)[label] - cost_giou * GIoU
+ * (torchvision's generalized_box_iou on the xyxy boxes, no epsilon).  A label outside [0, C1) gives NaN. */
+int mv_det_cost(const float* logits, const float* boxes, const int64_t* labels, const float* tboxes, const int32_t* toff,
+                float* out, float cost_class, float cost_bbox, float cost_giou, int B, int Q, int C1, mv_stream_t stream);
+/* detector.py:48-52,82-84: per-query targets from the matching.  match int32 [n]: flat target index of query i or -1 ->
+ * tgt_class int64 [n] (no_object where unmatched), tgt_box [n, 4] (zeros where unmatched). */
+int mv_det_assign(const int32_t* match, const int64_t* labels, const float* tboxes, int64_t* tgt_class, float* tgt_box, long n,
+                  long ntargets, int no_object, mv_stream_t stream);
+/* SetCriterion, detector.py:41-98, one launch each way.  weight [C1] (empty_weight), tcount int32 [B] (targets per image),
+ * inv_num_boxes = 1 / num_boxes (detector.py:134-138).  fwd: lse [B*Q] (kept for the backward), stats fp32 [8]:
+ * [0] loss_ce = sum w[t] nll / sum w[t], [1] loss_bbox = sum |d| / num_boxes, [2] loss_giou = sum (1 - GIoU) / num_boxes over the
+ * matched queries (tgt_class != C1 - 1), [3] class_error = 100 - top-1 accuracy over the matched queries (100 when none),
+ * [4] cardinality_error, [5] sum w[t], [6] matched queries, [7] target classes outside [0, C1) (then [0] is NaN).
+ * bwd: g_ce / g_bbox / g_giou: device scalars (NULL = 0), the incoming gradients of stats[0..2] -> dlogits [B, Q, C1], dboxes
+ * [B, Q, 4] (zero rows for unmatched queries), every element written once. */
+int mv_det_loss_fwd(const float* logits, const float* boxes, const int64_t* tgt_class, const float* tgt_box, const float* weight,
+                    const int32_t* tcount, float* lse, float* stats, float inv_num_boxes, int B, int Q, int C1,
+                    mv_stream_t stream);
+int mv_det_loss_bwd(const float* logits, const float* boxes, const int64_t* tgt_class, const float* tgt_box, const float* weight,
+                    const float* lse, const float* stats, const float* g_ce, const float* g_bbox, const float* g_giou,
+                    float* dlogits, float* dboxes, float inv_num_boxes, int B, int Q, int C1, mv_stream_t stream);
+/* PostProcess.forward, detector.py:159-176: scores [B, Q] / labels int64 [B, Q] = max / first arg-max of the softmax over the real
+ * classes, out_boxes [B, Q, 4] = xyxy * (w, h, w, h); sizes fp32 [B, 2] = (height, width). */
+int mv_det_postprocess(const float* logits, const float* boxes, const float* sizes, float* scores, int64_t* labels,
+                       float* out_boxes, int B, int Q, int C1, mv_stream_t stream);
+
 /* ---- image batch preparation: Normalize(ToTensor(hflip?(resize(crop(img, box), size, BILINEAR)))) ----
  * replaces the per-image torchvision/Pillow pipeline of the DataLoader worker (datasets/resisc45.py:40-69,
  * datasets/dlrsd.py:39-66, transforms/segmentation.py) on decoded uint8 frames, bit-exact to Pillow's 8-bit resampler.

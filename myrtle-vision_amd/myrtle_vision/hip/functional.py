@@ -989,6 +989,87 @@ def seg_head(x, g, b, w, bias, grid, size, prec):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# YOLOS detection: decoder, sequence assembly, set loss (csrc/detection.hip; fp32 in every precision)
+# ------------------------------------------------------------------------------------------------------------
+class _DetHeads(Function):
+    """DetectionDecoder: class_embed(x[:, -Q:]) and bbox_embed(x[:, -Q:]).sigmoid() (vit.py:389-396) in one pass over the
+    gathered rows -> fp32 (logits [B, Q, C + 1], boxes [B, Q, 4])."""
+
+    @staticmethod
+    def forward(ctx, x, w_cls, b_cls, w_box, b_box, Q):
+        ops.require_cuda(x, w_cls, b_cls, w_box, b_box)
+        ctx.set_materialize_grads(False)                      # an output the loss does not use arrives as None, not as zeros
+        x = _c(x.float())
+        logits, boxes = ops.det_heads_fwd(x, _c(w_cls.detach()), _c(b_cls.detach()), _c(w_box.detach()), _c(b_box.detach()), Q)
+        ctx.save_for_backward(x, w_cls, w_box, boxes)
+        ctx.params = (w_cls, b_cls, w_box, b_box)
+        ctx.Q = Q
+        return logits, boxes
+
+    @staticmethod
+    def backward(ctx, dlogits, dboxes):
+        x, w_cls, w_box, boxes = ctx.saved_tensors
+        dlogits = None if dlogits is None else _c(dlogits.float())
+        dboxes = None if dboxes is None else _c(dboxes.float())
+        dx, dwc, dbc, dwb, dbb = ops.det_heads_bwd(x, _c(w_cls.detach()), _c(w_box.detach()), boxes, dlogits, dboxes, ctx.Q,
+                                                   want_dx=ctx.needs_input_grad[0], params=ctx.params)
+        return dx, dwc, dbc, dwb, dbb, None
+
+
+def det_heads(x, w_cls, b_cls, w_box, b_box, num_det_tokens):
+    return _DetHeads.apply(x, w_cls, b_cls, w_box, b_box, num_det_tokens)
+
+
+class _DetAppend(Function):
+    """cat(x, det_tokens + pos_embedding_det) along the sequence (vit.py:285-302 with the detection branch taken)."""
+
+    @staticmethod
+    def forward(ctx, x, det_tokens, pos_det):
+        ops.require_cuda(x, det_tokens, pos_det)
+        Q, D = det_tokens.shape[-2:]
+        ctx.dims = (x.shape[1], Q, det_tokens.shape, pos_det.shape)
+        ctx.params = (det_tokens if det_tokens.is_leaf else None, pos_det if pos_det.is_leaf else None)
+        return ops.det_append_fwd(_c(x.float()), ops._f32c(det_tokens).view(Q, D), ops._f32c(pos_det).view(Q, D))
+
+    @staticmethod
+    def backward(ctx, dout):
+        T0, Q, det_shape, pos_shape = ctx.dims
+        dx, ddet, dpos = ops.det_append_bwd(_c(dout.float()), T0, Q, *ctx.params)
+        return dx, ddet.view(det_shape), dpos.view(pos_shape)
+
+
+def det_append(x, det_tokens, pos_det):
+    return _DetAppend.apply(x, det_tokens, pos_det)
+
+
+class _DetSetLoss(Function):
+    """SetCriterion's three differentiable scalars and two statistics (detector.py:41-98) from the per-query targets:
+    -> (loss_ce, loss_bbox, loss_giou, class_error, cardinality_error), one kernel each way."""
+
+    @staticmethod
+    def forward(ctx, logits, boxes, tgt_class, tgt_box, weight, tcount, num_boxes):
+        ctx.set_materialize_grads(False)
+        logits, boxes = _c(logits.float()), _c(boxes.float())
+        stats, lse = ops.det_loss_fwd(logits, boxes, tgt_class, tgt_box, weight, tcount, num_boxes)
+        ctx.save_for_backward(logits, boxes, tgt_class, tgt_box, weight, lse, stats)
+        ctx.num_boxes = num_boxes
+        out = stats[:5].unbind(0)
+        ctx.mark_non_differentiable(out[3], out[4])
+        return out
+
+    @staticmethod
+    def backward(ctx, g_ce, g_bbox, g_giou, _g3, _g4):
+        logits, boxes, tgt_class, tgt_box, weight, lse, stats = ctx.saved_tensors
+        g = [None if t is None else _c(t.float()) for t in (g_ce, g_bbox, g_giou)]
+        dlogits, dboxes = ops.det_loss_bwd(logits, boxes, tgt_class, tgt_box, weight, lse, stats, *g, ctx.num_boxes)
+        return dlogits, dboxes, None, None, None, None, None
+
+
+def det_set_loss(logits, boxes, tgt_class, tgt_box, weight, tcount, num_boxes):
+    return _DetSetLoss.apply(logits, boxes, tgt_class, tgt_box, weight, tcount, num_boxes)
+
+
+# ------------------------------------------------------------------------------------------------------------
 # loss
 # ------------------------------------------------------------------------------------------------------------
 class _CrossEntropy(Function):

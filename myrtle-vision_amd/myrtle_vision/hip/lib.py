@@ -98,6 +98,16 @@ SIGNATURES = {
     "mv_seg_ce_partials": ("iii", _L),
     "mv_seg_ce_fwd": ("pppppp" "iiiiii" "p", _I),
     "mv_seg_ce_bwd": ("ppppp" "ii" "f" "iiiiii" "p", _I),
+    "mv_det_heads_fwd": ("ppppppp" "iiiii" "p", _I),
+    "mv_det_heads_bwd_workspace_bytes": ("iiii", _Z),
+    "mv_det_heads_bwd": ("ppppppppppp" "pz" "iiiii" "p", _I),
+    "mv_det_append_fwd": ("pppp" "iiii" "p", _I),
+    "mv_det_append_bwd": ("pppp" "iiii" "p", _I),
+    "mv_det_cost": ("pppppp" "fff" "iii" "p", _I),
+    "mv_det_assign": ("ppppp" "ll" "i" "p", _I),
+    "mv_det_loss_fwd": ("pppppppp" "f" "iii" "p", _I),
+    "mv_det_loss_bwd": ("pppppppppppp" "f" "iii" "p", _I),
+    "mv_det_postprocess": ("pppppp" "iii" "p", _I),
     "mv_image_prepare": ("plii" "pppp" "i" "p" "ffffff" "p" "iii" "p", _I),
     "mv_mask_prepare": ("plii" "pp" "p" "i" "p" "iii" "p", _I),
     "mv_image_resize_u8": ("plii" "pppp" "i" "p" "iii" "p", _I),

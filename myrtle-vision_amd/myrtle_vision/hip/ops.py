@@ -1421,6 +1421,114 @@ def seg_ce_bwd(small, labels, lse, B, C, h, w, H, W, *, grad_dtype=torch.float32
     return ds
 
 
+# ------------------------------------------------------------------------------------------------------------
+# YOLOS detection tail (csrc/detection.hip): fp32 in every precision
+# ------------------------------------------------------------------------------------------------------------
+def _f32c(t):
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def det_heads_fwd(x, w_cls, b_cls, w_box, b_box, Q):
+    """x fp32 [B, T, D] -> (logits [B, Q, C1], boxes [B, Q, 4] after the sigmoid) from the last Q rows of every image."""
+    require_cuda(x, w_cls, b_cls, w_box, b_box)
+    B, T, D = x.shape
+    C1 = w_cls.shape[0]
+    logits = torch.empty(B, Q, C1, dtype=torch.float32, device=x.device)
+    boxes = torch.empty(B, Q, 4, dtype=torch.float32, device=x.device)
+    check(lib().mv_det_heads_fwd(_p(x), _p(w_cls), _p(b_cls), _p(w_box), _p(b_box), _p(logits), _p(boxes), B, T, Q, D, C1, _s()),
+          "det_heads_fwd", B=B, T=T, Q=Q, D=D, C1=C1)
+    return logits, boxes
+
+
+def det_heads_bwd(x, w_cls, w_box, boxes, dlogits, dboxes, Q, *, want_dx=True, params=(None, None, None, None)):
+    """-> (dx [B, T, D] or None, dw_cls, db_cls, dw_box, db_box); ``params``: the four parameters (gradient destinations)."""
+    B, T, D = x.shape
+    C1 = w_cls.shape[0]
+    dev = x.device
+    dx = torch.zeros_like(x) if want_dx else None                # the kernel writes the last Q rows of every image
+    dwc, dbc = grad_out(params[0], (C1, D), dev), grad_out(params[1], (C1,), dev)
+    dwb, dbb = grad_out(params[2], (4, D), dev), grad_out(params[3], (4,), dev)
+    ws = workspace(lib().mv_det_heads_bwd_workspace_bytes(B, Q, D, C1), dev)
+    check(lib().mv_det_heads_bwd(_p(x), _p(w_cls), _p(w_box), _p(boxes), _p(dlogits), _p(dboxes), _p(dx), _p(dwc), _p(dbc),
+                                 _p(dwb), _p(dbb), _p(ws), ws.numel(), B, T, Q, D, C1, _s()),
+          "det_heads_bwd", B=B, T=T, Q=Q, D=D, C1=C1)
+    return dx, dwc, dbc, dwb, dbb
+
+
+def det_append_fwd(x, det, pos):
+    """cat(x [B, T0, D], det [Q, D] + pos [Q, D]) -> [B, T0 + Q, D]."""
+    require_cuda(x, det, pos)
+    B, T0, D = x.shape
+    Q = det.shape[0]
+    out = torch.empty(B, T0 + Q, D, dtype=torch.float32, device=x.device)
+    check(lib().mv_det_append_fwd(_p(x), _p(det), _p(pos), _p(out), B, T0, Q, D, _s()), "det_append_fwd", B=B, T0=T0, Q=Q, D=D)
+    return out
+
+
+def det_append_bwd(dout, T0, Q, det=None, pos=None):
+    """dout [B, T0 + Q, D] -> (dx [B, T0, D], ddet [Q, D], dpos [Q, D])."""
+    B, T, D = dout.shape
+    dx = torch.empty(B, T0, D, dtype=torch.float32, device=dout.device)
+    ddet, dpos = grad_out(det, (Q, D), dout.device), grad_out(pos, (Q, D), dout.device)
+    check(lib().mv_det_append_bwd(_p(dout), _p(dx), _p(ddet), _p(dpos), B, T0, Q, D, _s()), "det_append_bwd", B=B, T0=T0, Q=Q,
+          D=D)
+    return dx, ddet, dpos
+
+
+def det_cost(logits, boxes, labels, tboxes, toff, total, cost_class, cost_bbox, cost_giou):
+    """Packed per-image cost blocks: fp32 [Q * total]; the [Q, T_b] block of image b starts at Q * toff[b]."""
+    require_cuda(logits, boxes, labels, tboxes, toff)
+    B, Q, C1 = logits.shape
+    out = torch.empty(Q * total, dtype=torch.float32, device=logits.device)
+    if total > 0:
+        check(lib().mv_det_cost(_p(logits), _p(boxes), _p(labels), _p(tboxes), _p(toff), _p(out), float(cost_class),
+                                float(cost_bbox), float(cost_giou), B, Q, C1, _s()), "det_cost", B=B, Q=Q, C1=C1)
+    return out
+
+
+def det_assign(match, labels, tboxes, B, Q, no_object):
+    """match int32 [B * Q] (flat target index or -1) -> (tgt_class int64 [B, Q], tgt_box fp32 [B, Q, 4])."""
+    require_cuda(match, labels, tboxes)
+    tgt_class = torch.empty(B, Q, dtype=torch.int64, device=match.device)
+    tgt_box = torch.empty(B, Q, 4, dtype=torch.float32, device=match.device)
+    check(lib().mv_det_assign(_p(match), _p(labels), _p(tboxes), _p(tgt_class), _p(tgt_box), B * Q, labels.numel(), no_object,
+                              _s()), "det_assign", B=B, Q=Q)
+    return tgt_class, tgt_box
+
+
+def det_loss_fwd(logits, boxes, tgt_class, tgt_box, weight, tcount, num_boxes):
+    """-> (stats fp32 [8]: loss_ce, loss_bbox, loss_giou, class_error, cardinality_error, sum of weights, matched, bad; lse)."""
+    require_cuda(logits, boxes, tgt_class, tgt_box, weight, tcount)
+    B, Q, C1 = logits.shape
+    stats = torch.empty(8, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(B * Q, dtype=torch.float32, device=logits.device)
+    check(lib().mv_det_loss_fwd(_p(logits), _p(boxes), _p(tgt_class), _p(tgt_box), _p(weight), _p(tcount), _p(lse), _p(stats),
+                                1.0 / num_boxes, B, Q, C1, _s()), "det_loss_fwd", B=B, Q=Q, C1=C1)
+    return stats, lse
+
+
+def det_loss_bwd(logits, boxes, tgt_class, tgt_box, weight, lse, stats, g_ce, g_bbox, g_giou, num_boxes):
+    B, Q, C1 = logits.shape
+    dlogits, dboxes = torch.empty_like(logits), torch.empty_like(boxes)
+    check(lib().mv_det_loss_bwd(_p(logits), _p(boxes), _p(tgt_class), _p(tgt_box), _p(weight), _p(lse), _p(stats), _p(g_ce),
+                                _p(g_bbox), _p(g_giou), _p(dlogits), _p(dboxes), 1.0 / num_boxes, B, Q, C1, _s()),
+          "det_loss_bwd", B=B, Q=Q, C1=C1)
+    return dlogits, dboxes
+
+
+def det_postprocess(logits, boxes, sizes):
+    """-> (scores [B, Q], labels int64 [B, Q], boxes xyxy scaled by (w, h, w, h) [B, Q, 4]); sizes [B, 2] = (height, width)."""
+    require_cuda(logits, boxes, sizes)
+    B, Q, C1 = logits.shape
+    scores = torch.empty(B, Q, dtype=torch.float32, device=logits.device)
+    labels = torch.empty(B, Q, dtype=torch.int64, device=logits.device)
+    out = torch.empty(B, Q, 4, dtype=torch.float32, device=logits.device)
+    check(lib().mv_det_postprocess(_p(logits), _p(boxes), _p(sizes), _p(scores), _p(labels), _p(out), B, Q, C1, _s()),
+          "det_postprocess", B=B, Q=Q, C1=C1)
+    return scores, labels, out
+
+
 def image_prepare(raw, kh, bh, kv, bv, flip, mean, std):
     """uint8 [B, Hs, Ws, 3] + Pillow resampling tables -> fp32 [B, 3, oh, ow] (crop/resize/flip/ToTensor/Normalize)."""
     require_cuda(raw, kh, bh, kv, bv, flip)

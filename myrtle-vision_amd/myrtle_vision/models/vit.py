@@ -365,6 +365,7 @@ class ViT(nn.Module):
         q_format: Optional[Union[str, QFormat]] = None,
         precision: Optional[str] = None,
         prune_dead_tokens: Optional[bool] = None,
+        live_det_tokens: bool = False,
     ):
         super().__init__()
         assert image_size % patch_size == 0, "Image dimensions must be divisible by the patch size."
@@ -383,7 +384,13 @@ class ViT(nn.Module):
         if heads * dim_head != dim:
             # the reference reshapes with c_dim // heads (vit.py:88), so it only works when heads*dim_head == dim
             raise ValueError(f"heads * dim_head must equal dim (got {heads} * {dim_head} != {dim})")
+        if live_det_tokens and decoder != "detection":
+            raise ValueError("live_det_tokens applies to decoder='detection' only")
         self.patch_size = patch_size
+        # Extension (off by default): the reference's ``self.decoder == "detection"`` compares a module with a string and is always
+        # False (vit.py:287,299), so as it runs the detection tokens are never concatenated and the decoder reads the last 100
+        # PATCH tokens.  True = what YOLOS intends: cat(cls, patches, det_tokens) + cat(pos_cls, resized grid, pos_embedding_det).
+        self.live_det_tokens = bool(live_det_tokens)
 
         if profile:
             self.cm_patch_to_embedding = profiler.record_function("patch_to_embedding")
@@ -441,8 +448,8 @@ class ViT(nn.Module):
         """Parameters that never reach the loss for the classification / segmentation decoders: the detection
         tokens are built but never concatenated (reference vit.py:285-290, ``self.decoder == "detection"`` is
         always False).  The optimizer and the gradient all-reduce leave them alone, exactly as
-        torch.optim skips parameters whose ``.grad`` is None."""
-        return ("pos_embedding_det", "det_tokens")
+        torch.optim skips parameters whose ``.grad`` is None.  With ``live_det_tokens`` they are part of the sequence: none."""
+        return () if self.live_det_tokens else ("pos_embedding_det", "det_tokens")
 
     # -- positional embedding (reference vit.py:292-302) ---------------------------------------------------
     def _pos_embedding(self, gh: int, gw: int) -> torch.Tensor:
@@ -516,6 +523,8 @@ class ViT(nn.Module):
                                   self._pos_embedding(gh, gw), p, self.precision)
         else:
             x = self._embed_unfused(img, gh, gw)
+        if self.live_det_tokens:
+            x = F.det_append(x, self.quant_det_tokens(self.det_tokens), self.pos_embedding_det)
         x = self.dropout(x)
 
         with self.cm_transformer:
@@ -531,7 +540,8 @@ class ViT(nn.Module):
         with self.cm_patch_to_embedding:
             x = F.cast(self.patch_to_embedding(x), torch.float32)
         cls_tokens = self.quant_cls_token(self.cls_token.repeat(b_dim, 1, 1))
-        # det tokens are built and never used for these decoders (reference vit.py:285-290)
+        # det tokens are built and never used by the reference as it runs (vit.py:285-290); live_det_tokens appends
+        # them after this function (_backbone)
         x = self.cls_token_cat.cat((cls_tokens, x), dim=1)
         pos = self.pos_embedding_cat.post(self._pos_embedding(gh, gw))   # the reference's cat of (cls slot, grid)
         return self.pos_embedding_add.add(x, self.quant_pos_embedding(pos.repeat(b_dim, 1, 1)))
@@ -608,8 +618,12 @@ class SegmentationDecoder(nn.Module):
                                g, self.image_size, self.norm.precision)
 
 
-# ---- reference vit.py:376-396 (detection is out of scope for the HIP path: SURVEY section 2 row 16) --------
+# ---- reference vit.py:376-396 -------------------------------------------------------------------------------
 class DetectionDecoder(nn.Module):
+    """YOLOS heads on the last ``num_det_tokens`` rows of the sequence -> {"pred_logits": [B, Q, C + 1], "pred_boxes":
+    [B, Q, 4]} in fp32 (every precision: the backbone alone follows ``precision``).  Both heads and the sigmoid run in one
+    pass over the Q gathered rows (``F.det_heads``), never over all N rows."""
+
     def __init__(self, in_dim, num_classes, num_det_tokens):
         super().__init__()
         self.class_embed = Linear(in_dim, num_classes + 1)
@@ -617,5 +631,15 @@ class DetectionDecoder(nn.Module):
         self.num_det_tokens = num_det_tokens
 
     def forward(self, x: torch.Tensor):
-        raise NotImplementedError(
-            "the detection decoder is outside the MI355X hot-path scope (classification + segmentation only)")
+        ops.require_cuda(x)
+        q = self.num_det_tokens
+        if x.dim() != 3 or x.shape[1] < q:
+            raise ValueError(f"expected a [B, N >= {q}, D] sequence, got {tuple(x.shape)}")
+        if _plain(self.class_embed, Linear) and _plain(self.bbox_embed, Linear):
+            logits, boxes = F.det_heads(x, self.class_embed.weight, self.class_embed.bias, self.bbox_embed.weight,
+                                        self.bbox_embed.bias, q)
+            return {"pred_logits": logits, "pred_boxes": boxes}
+        # module by module (reference vit.py:389-396): prepare_qat wrapped the heads, or something hooks into them
+        x = x[:, -q:, :]
+        return {"pred_logits": F.cast(self.class_embed(x), torch.float32),
+                "pred_boxes": F.cast(self.bbox_embed(x), torch.float32).sigmoid()}

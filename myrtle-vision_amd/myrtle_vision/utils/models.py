@@ -18,7 +18,9 @@ from myrtle_vision.utils.utils import parse_config
 
 
 def get_models(config, profile=False):
-    """reference utils/models.py:25-60 -> (vit, distiller=None).  Optional extension key ``vit_config["precision"]``."""
+    """reference utils/models.py:25-60 -> (vit, distiller=None).  Optional extension keys ``vit_config["precision"]`` and, for
+    ``decoder: "detection"``, ``vit_config["live_det_tokens"]`` (ViT's opt-in YOLOS sequence assembly; the criterion, matcher and
+    post-processing live in ``myrtle_vision.models.detector`` / ``.matcher``)."""
     vit_config = config["vit_config"]
     data_config = parse_config(config["data_config_path"])
     if "distiller_config" in config:
@@ -38,6 +40,8 @@ def get_models(config, profile=False):
         "q_format": QFormat[vit_config["q_format"]],
         "precision": vit_config.get("precision"),
     }
+    if vit_config.get("live_det_tokens"):
+        vit_kwargs["live_det_tokens"] = True
     return ViT(**vit_kwargs), None
 
 
