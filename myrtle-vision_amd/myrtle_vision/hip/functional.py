@@ -273,52 +273,35 @@ def dropout(x, p, training=True):
 
 
 class _AttentionFused(Function):
-    """softmax(q k^T * scale) v on the fused MFMA kernel.  qkv bf16 [B, N, 3*H*64] -> [B, N, H*64]."""
+    """softmax(q k^T * scale) v on the fused kernels of one ``ops.attention_path`` (any but the materialised one; no [B, H, N, N]
+    tensor): saves qkv, out and the log-sum-exp, the backward kernels recompute the probabilities.  qkv [B, N, 3*H*dh] ->
+    [B, N, H*dh] in qkv's dtype.  The decorators are for the Linear products of other functions: no attention kernel on these
+    paths reads the split memo or the segment count."""
 
     @staticmethod
     @_fwd
-    def forward(ctx, qkv, heads, scale):
-        B, N, three_d = qkv.shape
-        qkv = _c(qkv)
-        out, lse = ops.attention_fwd(qkv, B, N, heads, scale)
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.heads, ctx.scale = heads, scale
-        return out
-
-    @staticmethod
-    @_scoped
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        B, N, _ = qkv.shape
-        dout = _c(dout)
-        if dout.dtype != torch.bfloat16:
-            dout = ops.cast(dout, torch.bfloat16)
-        return ops.attention_bwd(qkv, out, dout, lse, B, N, ctx.heads, ctx.scale), None, None
-
-
-class _AttentionFusedDh(Function):
-    """``_AttentionFused`` for the head widths of ``ops.ATTN_DH_WIDTHS`` (32, 128).  qkv bf16 [B, N, 3*H*dh] -> [B, N, H*dh]."""
-
-    @staticmethod
-    @_fwd
-    def forward(ctx, qkv, heads, scale):
+    def forward(ctx, path, qkv, heads, scale):
         B, N, three_d = qkv.shape
         qkv = _c(qkv)
         dh = three_d // (3 * heads)
-        out, lse = ops.attention_fwd_dh(qkv, B, N, heads, dh, scale)
+        out, lse = ops.attention_forward(path, qkv, B, N, heads, dh, scale)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.heads, ctx.dh, ctx.scale = heads, dh, scale
+        ctx.cfg = (path, heads, dh, scale)
         return out
 
     @staticmethod
     @_scoped
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
+        path, heads, dh, scale = ctx.cfg
         B, N, _ = qkv.shape
-        dout = _c(dout)
-        if dout.dtype != torch.bfloat16:
-            dout = ops.cast(dout, torch.bfloat16)
-        return ops.attention_bwd_dh(qkv, out, dout, lse, B, N, ctx.heads, ctx.dh, ctx.scale), None, None
+        if qkv.dtype == torch.bfloat16:                  # the kernels read dO in q/k/v's format
+            dout = _c(dout)
+            if dout.dtype != torch.bfloat16:
+                dout = ops.cast(dout, torch.bfloat16)
+        else:
+            dout = _c(dout.float())
+        return None, ops.attention_backward(path, qkv, out, dout, lse, B, N, heads, dh, scale), None, None
 
 
 class _AttentionProbs(Function):
@@ -389,27 +372,6 @@ class _AttentionPV(Function):
         return dP, dqkv, None
 
 
-class _AttentionFusedF32(Function):
-    """The fp32 attention core with gradients, fused both ways (no [B, H, N, N] tensor): saves qkv, out and the
-    log-sum-exp; the backward kernel recomputes the probabilities."""
-
-    @staticmethod
-    def forward(ctx, qkv, heads, scale):
-        B, N, _ = qkv.shape
-        qkv = _c(qkv)
-        out, lse = ops.attention_fwd_f32_lse(qkv, B, N, heads, scale)
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.cfg = (heads, scale)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        heads, scale = ctx.cfg
-        B, N, _ = qkv.shape
-        return ops.attention_bwd_f32_fused(qkv, out, _c(dout.float()), lse, B, N, heads, scale), None, None
-
-
 def attention_core(qkv, heads, scale, probs_hook=None):
     """Attention.forward lines vit.py:87-96 on a to_qkv output [B, N, 3*heads*dh].
 
@@ -418,16 +380,10 @@ def attention_core(qkv, heads, scale, probs_hook=None):
     fused kernels (head widths 64, 32 and 128)."""
     B, N, three_d = qkv.shape
     dh = three_d // (3 * heads)
-    if probs_hook is None and ops.attention_fused_supported(qkv.dtype, N, dh):
-        return _AttentionFused.apply(qkv, heads, scale)
-    if probs_hook is None and ops.attention_dh_supported(qkv.dtype, N, dh):
-        return _AttentionFusedDh.apply(qkv, heads, scale)
-    if (probs_hook is None and ops.attention_f32_fused_supported(qkv.dtype, N, dh)
-            and not (torch.is_grad_enabled() and qkv.requires_grad)):
-        # no gradient wanted (converted int8 model, fp32 evaluation): exact fp32 arithmetic without the probabilities
-        return ops.attention_fwd_f32(_c(qkv), B, N, heads, scale)
-    if probs_hook is None and ops.attention_f32_fused_supported(qkv.dtype, N, dh):
-        return _AttentionFusedF32.apply(qkv, heads, scale)          # fp32 with gradients: fused forward + backward
+    path = ops.attention_path(qkv.dtype, N, dh, need_grad=torch.is_grad_enabled() and qkv.requires_grad,
+                              hook=probs_hook is not None)
+    if path != ops.ATTN_PROBS:
+        return _AttentionFused.apply(path, qkv, heads, scale)
     src_dtype = qkv.dtype
     q32 = cast(qkv, torch.float32)
     probs = _AttentionProbs.apply(q32, heads, scale)
@@ -573,61 +529,36 @@ class _AttnBlock(Function):
             dh = inner // heads
             # LayerNorm writes the pieces itself (no fp32 y, no split pass)
             y6, mean, rstd = ops.layernorm_fwd_split(x, D, M, D, g, b) if D <= 1024 else (ops.split_ex(y, M, D), mean, rstd)
-            ctx.f16 = ops.attention_f16_supported(adt, T, dh)
+            ctx.path = path = ops.attention_path(adt, T, dh, need_grad=any(ctx.needs_input_grad), half_ok=True)
             # precision "bf16x3h": the fused attention kernels on half operands (2^-12 per rounding, fp32 sums, softmax and outputs);
             # q / k / v leave the to_qkv product as half (one rounding of the fp32 accumulator + bias, no fp32 tensor, no cast pass)
-            qkv = torch.empty(B, T, inner3, dtype=torch.float16 if ctx.f16 else adt, device=x.device)
+            qkv = torch.empty(B, T, inner3, dtype=torch.float16 if path == ops.ATTN_F16 else adt, device=x.device)
             ops.nt_x6(y6, wqkv, "fwd", M, qkv.view(M, inner3), bias=bqkv)
-            o = None
-            if ctx.f16:
-                o, probs = ops.attention_fwd_f16(qkv, B, T, heads, scale)            # "probs" slot: the log-sum-exp [B, H, T]
-                ctx.fused32 = True
-            elif ops.attention_f32_fused_supported(adt, T, dh):
-                if any(ctx.needs_input_grad):
-                    o, probs = ops.attention_fwd_f32_lse(qkv, B, T, heads, scale)   # "probs" slot: the log-sum-exp [B, H, T]
-                else:
-                    o, probs = ops.attention_fwd_f32(qkv, B, T, heads, scale), x.new_empty(0)   # evaluation
-                ctx.fused32 = True
-            else:
-                probs = ops.attention_probs_fp32(qkv, B, T, heads, dh, scale)
-                o = ops.attention_pv_fp32(probs, qkv, B, T, heads, dh)
-                ctx.fused32 = False
+            o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
             o6 = ops.split_ex(o.view(M, inner), M, inner)
             out = torch.empty_like(x)
             ops.nt_x6(o6, wo, "fwd", M, out.view(M, D), bias=bo, residual=x.view(M, D))
             # the fused backward needs the attention output itself (delta = rowsum(dO * O)), not only its split
-            ctx.save_for_backward(x, g, mean, rstd, y6, qkv, o6, probs, wqkv, wo, *((o,) if ctx.fused32 else ()))
-            ctx.cfg = (heads, scale, False)
+            ctx.save_for_backward(x, g, mean, rstd, y6, qkv, None if path == ops.ATTN_PROBS else o, o6, saved, wqkv, wo)
+            ctx.cfg = (heads, scale)
             ctx.small = (b, bqkv, bo)
             _chain_set(out, bo)
             return out
         qkv = torch.empty(B, T, inner3, dtype=adt, device=x.device)
         ops.linear_fwd(y, M, D, wqkv, bqkv, qkv, inner3)
         dh = inner // heads
-        if ops.attention_fused_supported(adt, T, dh):
-            o, lse = ops.attention_fwd(qkv, B, T, heads, scale)
-            probs = None
-        elif ops.attention_dh_supported(adt, T, dh):             # 32- and 128-wide heads: kernels of their own
-            o, lse = ops.attention_fwd_dh(qkv, B, T, heads, dh, scale)
-            probs = None
-        elif ops.attention_f32_fused_supported(adt, T, dh) and not any(ctx.needs_input_grad):
-            # fp32 evaluation: nothing will run backward, so the probabilities need not exist
-            o, lse, probs = ops.attention_fwd_f32(qkv, B, T, heads, scale), None, None
-        elif ops.attention_f32_fused_supported(adt, T, dh):
-            # fp32 training: fused forward + backward kernels, the log-sum-exp rides in the probabilities' slot
-            o, probs = ops.attention_fwd_f32_lse(qkv, B, T, heads, scale)
-            lse, ctx.fused32 = None, True
-        else:                                   # materialised fp32 probabilities (shapes the fused kernels lack)
-            q32 = ops.cast(qkv, torch.float32)
-            probs = ops.attention_probs_fp32(q32, B, T, heads, dh, scale)
-            o = ops.cast(ops.attention_pv_fp32(probs, q32, B, T, heads, dh), adt)
-            lse = None
+        # half_ok stays off: q/k/v and dO are in ``adt`` here, so of ops.ATTN_COLSUM_PATHS only the two bf16 ones can come back
+        ctx.path = path = ops.attention_path(adt, T, dh, need_grad=any(ctx.needs_input_grad))
+        assert path != ops.ATTN_F16
+        if path == ops.ATTN_PROBS:              # materialised fp32 probabilities (shapes the fused kernels lack)
+            o, saved = ops.attention_forward(path, ops.cast(qkv, torch.float32), B, T, heads, dh, scale)
+            o = ops.cast(o, adt)
+        else:
+            o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
         out = torch.empty_like(x)
         ops.linear_fwd(o.view(M, inner), M, inner, wo, bo, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
-        if lse is None and probs is None:        # evaluation-only path above
-            probs = x.new_empty(0)
-        ctx.save_for_backward(x, g, mean, rstd, y, qkv, o, lse if lse is not None else probs, wqkv, wo)
-        ctx.cfg = (heads, scale, lse is not None)
+        ctx.save_for_backward(x, g, mean, rstd, y, qkv, o, None, saved, wqkv, wo)
+        ctx.cfg = (heads, scale)
         ctx.small = (b, bqkv, bo)
         _chain_set(out, bo)
         return out
@@ -635,16 +566,18 @@ class _AttnBlock(Function):
     @staticmethod
     @_scoped
     def backward(ctx, dout):
-        x, g, mean, rstd, y, qkv, o, lse_or_probs, wqkv, wo = ctx.saved_tensors[:10]
-        heads, scale, fused = ctx.cfg
+        # y and o6 are bf16 pieces [M, nseg * cols] in the split-operand branch (o6 exists only there); ``saved`` is what
+        # ops.attention_forward returned on ctx.path: the log-sum-exp, the probabilities, or None (nothing runs backward then)
+        x, g, mean, rstd, y, qkv, o, o6, saved, wqkv, wo = ctx.saved_tensors
+        heads, scale = ctx.cfg
         B, T, D = x.shape
         M = B * T
         inner3 = wqkv.shape[0]
         inner = inner3 // 3
+        dh = inner // heads
+        b, bqkv, bo = ctx.small
+        dout = _c(dout)
         if ctx.x6:
-            y6, o6, probs = y, o, lse_or_probs
-            dout = _c(dout)
-            b, bqkv, bo = ctx.small
             d6, dbo = _take_side(dout, M, D, ("split", ops.current_segments()))   # the producing LayerNorm backward left both
             if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
                 dbo = ops.grad_out(bo, (D,), x.device)
@@ -653,47 +586,38 @@ class _AttnBlock(Function):
             do = torch.empty(B, T, inner, dtype=torch.float32, device=x.device)
             ops.nt_x6(d6, wo, "dx", M, do.view(M, inner))
             dbqkv = ops.grad_out(bqkv, (inner3,), x.device)
-            if ctx.f16:
+            if ctx.path == ops.ATTN_F16:
                 # the kernel writes the pieces of dqkv and per-image column sums itself: no fp32 dqkv, no split pass
                 part = torch.empty(B, inner3, dtype=torch.float32, device=x.device)
-                dq6 = ops.attention_bwd_f16(qkv, ctx.saved_tensors[10], do, probs, B, T, heads, scale, split=True, colsum=part)
+                dq6 = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale, split=True, colsum=part)
                 ops.colsum(part, B, inner3, inner3, dbqkv)
             else:
-                if ctx.fused32:
-                    dqkv = ops.attention_bwd_f32_fused(qkv, ctx.saved_tensors[10], do, probs, B, T, heads, scale)
-                else:
-                    dqkv = ops.attention_bwd_fp32(probs, qkv, do, B, T, heads, inner // heads, scale)
+                dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale)
                 dq6 = ops.split_ex(dqkv.view(M, inner3), M, inner3, colsum_out=dbqkv)
-            dwqkv = ops.tn_x6(dq6, y6, M, wqkv)
+            dwqkv = ops.tn_x6(dq6, y, M, wqkv)
             dy = torch.empty(M, D, dtype=torch.float32, device=x.device)
             ops.nt_x6(dq6, wqkv, "dx", M, dy)
             dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, torch.float32, ctx.up_bias)
             return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None
         adt = y.dtype
-        dout = _c(dout)
         d_act, dbo = _take_side(dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
         if d_act is None:
             d_act = ops.cast(dout, adt).view(M, D)                # dY of the projection, activation dtype
-        b, bqkv, bo = ctx.small
         dwo, dbo2 = ops.linear_dw(d_act, o.view(M, inner), M, D, inner, want_bias=dbo is None, weight=wo, bias=bo)
         dbo = dbo if dbo is not None else dbo2
         do = torch.empty(B, T, inner, dtype=adt, device=x.device)
         ops.linear_dx(d_act, M, D, wo, do, inner)
         dbqkv = None
-        if fused:
+        if ctx.path in ops.ATTN_COLSUM_PATHS:
             # the kernel also leaves per-image column sums of dqkv: to_qkv's bias gradient without another pass over dqkv
             part = torch.empty(B, inner3, dtype=torch.float32, device=x.device)
-            dh = inner // heads
-            if dh == 64:
-                dqkv = ops.attention_bwd(qkv, o, do, lse_or_probs, B, T, heads, scale, colsum=part)
-            else:
-                dqkv = ops.attention_bwd_dh(qkv, o, do, lse_or_probs, B, T, heads, dh, scale, colsum=part)
+            dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale, colsum=part)
             dbqkv = ops.colsum(part, B, inner3, inner3, ops.grad_out(bqkv, (inner3,), x.device))
-        elif getattr(ctx, "fused32", False):
-            dqkv = ops.attention_bwd_f32_fused(qkv, o, do, lse_or_probs, B, T, heads, scale)
+        elif ctx.path == ops.ATTN_PROBS:
+            dqkv = ops.cast(ops.attention_backward(ctx.path, ops.cast(qkv, torch.float32), None, ops.cast(do, torch.float32), saved,
+                                                   B, T, heads, dh, scale), adt)
         else:
-            dqkv = ops.cast(ops.attention_bwd_fp32(lse_or_probs, ops.cast(qkv, torch.float32), ops.cast(do, torch.float32),
-                                                   B, T, heads, inner // heads, scale), adt)
+            dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale)
         dwqkv, dbq2 = ops.linear_dw(dqkv.view(M, inner3), y, M, inner3, D, want_bias=dbqkv is None, weight=wqkv, bias=bqkv)
         dbqkv = dbqkv if dbqkv is not None else dbq2
         dy = torch.empty(M, D, dtype=adt, device=x.device)

@@ -821,10 +821,13 @@ def colsum(x, rows, cols, ld, out):
 # ------------------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------------------
+# The length caps and widths below restate the MV_REQUIRE lines of the C entry points; tests/test_attention_path.py probes the
+# built library at each cap and one past it, so the two cannot drift apart.
 ATTN_SHORT_MAX_N = 320      # the whole-head kernels (mv_attention_fwd / _bwd): K and V of a head in LDS
 ATTN_LONG_MAX_N = 8192      # the key-tiled kernels (mv_attention_fwd_long / _bwd_long, and their half forms _long_f16)
 ATTN_F16_SHORT_MAX_N = 288  # the whole-head half kernels (mv_attention_fwd_f16 / _bwd_f16)
 ATTN_F32_SHORT_MAX_N = 272  # the whole-head fp32 kernels (mv_attention_fwd_f32 / _f32_lse / _f32_q8 / _bwd_f32)
+ATTN_DH_WIDTHS = (32, 128)  # head widths other than 64 with fused bf16 kernels (mv_attention_fwd_dh / _bwd_dh), any N <= 8192
 # A/B switch for tools/bench_long_step.py only: False sends bf16 attention with N > 320, the half attention of bf16x3h with
 # N > 288, the fp32 attention of fp32 / bf16x3 with N > 272 and bf16 attention with 32- or 128-wide heads (any N) back to the
 # materialised fp32 path
@@ -836,75 +839,10 @@ def attention_fused_supported(qkv_dtype, N, dim_head):
     return qkv_dtype == torch.bfloat16 and dim_head == 64 and N <= cap
 
 
-def attention_fwd(qkv, B, N, H, scale):
-    """qkv bf16 [B, N, 3*H*64] -> (out bf16 [B, N, H*64], lse fp32 [B, H, N]); N > 320 takes the key-tiled kernel."""
-    if N > ATTN_SHORT_MAX_N:
-        return attention_fwd_long(qkv, B, N, H, scale)
-    require_cuda(qkv)
-    out = torch.empty(B, N, H * 64, dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-    check(lib().mv_attention_fwd(_p(qkv), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd", B=B, N=N, H=H)
-    return out, lse
-
-
-def attention_bwd(qkv, out, dout, lse, B, N, H, scale, colsum=None):
-    """-> dqkv.  ``colsum`` (optional fp32 [B, 3*H*64]) receives per-image column sums of dqkv (bias-gradient partials).
-    N > 320 takes the key-tiled kernels."""
-    if N > ATTN_SHORT_MAX_N:
-        return attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=colsum)
-    dqkv = torch.empty_like(qkv)
-    check(lib().mv_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(colsum), B, N, H, scale, _s()),
-          "attention_bwd", B=B, N=N, H=H)
-    return dqkv
-
-
-ATTN_DH_WIDTHS = (32, 128)  # head widths other than 64 with fused bf16 kernels (mv_attention_fwd_dh / _bwd_dh), any N <= 8192
-
-
 def attention_dh_supported(qkv_dtype, N, dim_head):
     """The key-tiled bf16 kernels for the head widths in ``ATTN_DH_WIDTHS`` (64 has kernels of its own: ``attention_fused_supported``):
     bf16 q/k/v, N <= 8192.  They are key-tiled kernels, so ``ATTN_LONG`` off sends these widths back to the materialised path too."""
     return ATTN_LONG and qkv_dtype == torch.bfloat16 and dim_head in ATTN_DH_WIDTHS and N <= ATTN_LONG_MAX_N
-
-
-def attention_fwd_dh(qkv, B, N, H, dim_head, scale):
-    """qkv bf16 [B, N, 3*H*dim_head] -> (out bf16 [B, N, H*dim_head], lse fp32 [B, H, N]); dim_head 32 or 128, any N <= 8192."""
-    require_cuda(qkv)
-    out = torch.empty(B, N, H * dim_head, dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-    check(lib().mv_attention_fwd_dh(_p(qkv), _p(out), _p(lse), B, N, H, dim_head, scale, _s()), "attention_fwd_dh", B=B, N=N, H=H,
-          dim_head=dim_head)
-    return out, lse
-
-
-def attention_bwd_dh(qkv, out, dout, lse, B, N, H, dim_head, scale, colsum=None):
-    """-> dqkv, as ``attention_bwd_long`` for dim_head 32 or 128 (``colsum``: optional fp32 [B, 3*H*dim_head]); the delta workspace
-    is a torch allocation (graph capture)."""
-    require_cuda(qkv, out, dout, lse)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-    check(lib().mv_attention_bwd_dh(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(colsum), B, N, H, dim_head, scale,
-                                    _s()), "attention_bwd_dh", B=B, N=N, H=H, dim_head=dim_head)
-    return dqkv
-
-
-def attention_fwd_long(qkv, B, N, H, scale):
-    """The key-tiled forward (any N <= 8192): as ``attention_fwd``."""
-    require_cuda(qkv)
-    out = torch.empty(B, N, H * 64, dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-    check(lib().mv_attention_fwd_long(_p(qkv), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_long", B=B, N=N, H=H)
-    return out, lse
-
-
-def attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=None):
-    """The key-tiled backward (any N <= 8192): as ``attention_bwd``; the delta workspace is a torch allocation (graph capture)."""
-    require_cuda(qkv, out, dout, lse)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-    check(lib().mv_attention_bwd_long(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(colsum), B, N, H, scale,
-                                      _s()), "attention_bwd_long", B=B, N=N, H=H)
-    return dqkv
 
 
 def attention_f32_fused_supported(qkv_dtype, N, dim_head):
@@ -921,6 +859,140 @@ def attention_f16_supported(qkv_dtype, N, dim_head):
     return qkv_dtype == torch.float32 and dim_head == 64 and N <= cap and half_attention()
 
 
+# One name per forward / backward pair of wrappers.  ``attention_path`` is the only place a family is chosen; the forward
+# records the name and ``attention_backward`` takes it back, so the two cannot disagree.
+ATTN_BF16 = "bf16"            # attention_fwd / attention_bwd: bf16 q/k/v, 64-wide heads
+ATTN_BF16_DH = "bf16_dh"      # attention_fwd_dh / attention_bwd_dh: bf16 q/k/v, the widths of ATTN_DH_WIDTHS
+ATTN_F16 = "f16"              # attention_fwd_f16 / attention_bwd_f16: half q/k/v, fp32 out (precision "bf16x3h")
+ATTN_F32 = "f32"              # attention_fwd_f32_lse / attention_bwd_f32_fused: exact fp32, keeps the log-sum-exp
+ATTN_F32_EVAL = "f32_eval"    # attention_fwd_f32: exact fp32, nothing kept, no backward
+ATTN_PROBS = "probs"          # attention_probs_fp32 + attention_pv_fp32 / attention_bwd_fp32: fp32 [B, H, N, N] probabilities
+ATTN_COLSUM_PATHS = (ATTN_BF16, ATTN_BF16_DH, ATTN_F16)     # whose backward kernels fill ``colsum`` themselves
+
+
+def attention_path(qkv_dtype, N, dim_head, *, need_grad, half_ok=False, hook=False):
+    """Which family computes the attention core of q/k/v in ``qkv_dtype`` (for ``ATTN_F16``: the dtype they have before the half
+    rounding, fp32).  ``need_grad`` only tells the two exact-fp32 paths apart; ``half_ok``: the caller can produce half q/k/v
+    (the split-operand block inside a "bf16x3h" scope); ``hook``: somebody wants to see the probabilities."""
+    if hook:
+        return ATTN_PROBS
+    if attention_fused_supported(qkv_dtype, N, dim_head):
+        return ATTN_BF16
+    if attention_dh_supported(qkv_dtype, N, dim_head):
+        return ATTN_BF16_DH
+    if half_ok and attention_f16_supported(qkv_dtype, N, dim_head):
+        return ATTN_F16
+    if attention_f32_fused_supported(qkv_dtype, N, dim_head):
+        return ATTN_F32 if need_grad else ATTN_F32_EVAL
+    return ATTN_PROBS
+
+
+def attention_forward(path, qkv, B, N, H, dim_head, scale):
+    """-> (out, saved) on ``path``: saved = the log-sum-exp (the fused paths), the probabilities (``ATTN_PROBS``, which takes fp32
+    q/k/v and gives fp32 out: the casts are the caller's) or None (``ATTN_F32_EVAL``)."""
+    if path == ATTN_BF16:
+        return attention_fwd(qkv, B, N, H, scale)
+    if path == ATTN_BF16_DH:
+        return attention_fwd_dh(qkv, B, N, H, dim_head, scale)
+    if path == ATTN_F16:
+        return attention_fwd_f16(qkv, B, N, H, scale)
+    if path == ATTN_F32:
+        return attention_fwd_f32_lse(qkv, B, N, H, scale)
+    if path == ATTN_F32_EVAL:
+        return attention_fwd_f32(qkv, B, N, H, scale), None
+    if path == ATTN_PROBS:
+        probs = attention_probs_fp32(qkv, B, N, H, dim_head, scale)
+        return attention_pv_fp32(probs, qkv, B, N, H, dim_head), probs
+    raise ValueError(f"attention_forward: unknown path {path!r}")
+
+
+def attention_backward(path, qkv, out, dout, saved, B, N, H, dim_head, scale, *, split=False, colsum=None):
+    """-> dqkv from what ``attention_forward(path, ...)`` took and returned (``out`` is not read on ``ATTN_PROBS``).  ``colsum``
+    (fp32 [B, 3*H*dim_head]: per-image column sums of dqkv) is filled by the paths of ``ATTN_COLSUM_PATHS`` only and ``split``
+    (dqkv as its bf16 pieces) exists on ``ATTN_F16`` only: elsewhere the caller takes both from a pass over dqkv."""
+    assert colsum is None or path in ATTN_COLSUM_PATHS, f"attention path {path!r} does not fill colsum"
+    assert not split or path == ATTN_F16, f"attention path {path!r} does not write split dqkv"
+    if path == ATTN_BF16:
+        return attention_bwd(qkv, out, dout, saved, B, N, H, scale, colsum=colsum)
+    if path == ATTN_BF16_DH:
+        return attention_bwd_dh(qkv, out, dout, saved, B, N, H, dim_head, scale, colsum=colsum)
+    if path == ATTN_F16:
+        return attention_bwd_f16(qkv, out, dout, saved, B, N, H, scale, split=split, colsum=colsum)
+    if path == ATTN_F32:
+        return attention_bwd_f32_fused(qkv, out, dout, saved, B, N, H, scale)
+    if path == ATTN_PROBS:
+        return attention_bwd_fp32(saved, qkv, dout, B, N, H, dim_head, scale)
+    raise ValueError(f"attention_backward: path {path!r} has no backward")
+
+
+# Workspaces and results are torch allocations throughout (graph capture).
+def _attn_rows(like, B, N, H):
+    """fp32 [B, H, N]: one value per query row -- a log-sum-exp, or the delta workspace of a key-tiled backward."""
+    return torch.empty(B, H, N, dtype=torch.float32, device=like.device)
+
+
+def _attn_out(qkv, B, N, H, dtype, dim_head=64):
+    """(out [B, N, H*dim_head] in ``dtype``, lse fp32 [B, H, N])."""
+    return torch.empty(B, N, H * dim_head, dtype=dtype, device=qkv.device), _attn_rows(qkv, B, N, H)
+
+
+def attention_fwd(qkv, B, N, H, scale):
+    """qkv bf16 [B, N, 3*H*64] -> (out bf16 [B, N, H*64], lse fp32 [B, H, N]); N > 320 takes the key-tiled kernel."""
+    if N > ATTN_SHORT_MAX_N:
+        return attention_fwd_long(qkv, B, N, H, scale)
+    require_cuda(qkv)
+    out, lse = _attn_out(qkv, B, N, H, torch.bfloat16)
+    check(lib().mv_attention_fwd(_p(qkv), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd", B=B, N=N, H=H)
+    return out, lse
+
+
+def attention_bwd(qkv, out, dout, lse, B, N, H, scale, colsum=None):
+    """-> dqkv.  ``colsum`` (optional fp32 [B, 3*H*64]) receives per-image column sums of dqkv (bias-gradient partials).
+    N > 320 takes the key-tiled kernels."""
+    if N > ATTN_SHORT_MAX_N:
+        return attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=colsum)
+    dqkv = torch.empty_like(qkv)
+    check(lib().mv_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(colsum), B, N, H, scale, _s()),
+          "attention_bwd", B=B, N=N, H=H)
+    return dqkv
+
+
+def attention_fwd_long(qkv, B, N, H, scale):
+    """The key-tiled forward (any N <= 8192): as ``attention_fwd``."""
+    require_cuda(qkv)
+    out, lse = _attn_out(qkv, B, N, H, torch.bfloat16)
+    check(lib().mv_attention_fwd_long(_p(qkv), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_long", B=B, N=N, H=H)
+    return out, lse
+
+
+def attention_bwd_long(qkv, out, dout, lse, B, N, H, scale, colsum=None):
+    """The key-tiled backward (any N <= 8192): as ``attention_bwd``; the delta workspace is a torch allocation (graph capture)."""
+    require_cuda(qkv, out, dout, lse)
+    dqkv, delta = torch.empty_like(qkv), _attn_rows(qkv, B, N, H)
+    check(lib().mv_attention_bwd_long(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(colsum), B, N, H, scale,
+                                      _s()), "attention_bwd_long", B=B, N=N, H=H)
+    return dqkv
+
+
+def attention_fwd_dh(qkv, B, N, H, dim_head, scale):
+    """qkv bf16 [B, N, 3*H*dim_head] -> (out bf16 [B, N, H*dim_head], lse fp32 [B, H, N]); dim_head 32 or 128, any N <= 8192."""
+    require_cuda(qkv)
+    out, lse = _attn_out(qkv, B, N, H, torch.bfloat16, dim_head)
+    check(lib().mv_attention_fwd_dh(_p(qkv), _p(out), _p(lse), B, N, H, dim_head, scale, _s()), "attention_fwd_dh", B=B, N=N, H=H,
+          dim_head=dim_head)
+    return out, lse
+
+
+def attention_bwd_dh(qkv, out, dout, lse, B, N, H, dim_head, scale, colsum=None):
+    """-> dqkv, as ``attention_bwd_long`` for dim_head 32 or 128 (``colsum``: optional fp32 [B, 3*H*dim_head]); the delta workspace
+    is a torch allocation (graph capture)."""
+    require_cuda(qkv, out, dout, lse)
+    dqkv, delta = torch.empty_like(qkv), _attn_rows(qkv, B, N, H)
+    check(lib().mv_attention_bwd_dh(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(colsum), B, N, H, dim_head, scale,
+                                    _s()), "attention_bwd_dh", B=B, N=N, H=H, dim_head=dim_head)
+    return dqkv
+
+
 def cast_f16(src):
     """fp32 -> IEEE half (stored in a torch.float16 tensor)."""
     require_cuda(src)
@@ -933,10 +1005,28 @@ def attention_fwd_f16(qkv16, B, N, H, scale):
     """-> (out fp32 [B, N, H*64], lse fp32 [B, H, N]) from half q/k/v [B, N, 3, H, 64]; N > 288 takes the key-tiled kernel."""
     if N > ATTN_F16_SHORT_MAX_N:
         return attention_fwd_long_f16(qkv16, B, N, H, scale)
-    out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv16.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv16.device)
+    out, lse = _attn_out(qkv16, B, N, H, torch.float32)
     check(lib().mv_attention_fwd_f16(_p(qkv16), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_f16", B=B, N=N, H=H)
     return out, lse
+
+
+def _attention_bwd_prep_f16(out, dout, B, N, H):
+    """dout fp32 -> (dout16 half scaled per (image, head) by gscale, delta = rowsum(dout16 * out), gscale fp32 [B * H])."""
+    dout16 = torch.empty(B, N, H * 64, dtype=torch.float16, device=out.device)
+    delta = _attn_rows(out, B, N, H)
+    gscale = torch.empty(B * H, dtype=torch.float32, device=out.device)
+    check(lib().mv_attention_bwd_prep_f16(_p(dout), _p(out), _p(dout16), _p(delta), _p(gscale), B, N, H, _s()),
+          "attention_bwd_prep_f16", B=B, N=N, H=H)
+    return dout16, delta, gscale
+
+
+def _attention_bwd_start_f16(out, dout, B, N, H, split):
+    """What both half backwards start from: the prep pass, then -> (dout16, delta, gscale, dqkv, nseg) with dqkv the fp32 result
+    buffer [B, N, 3*H*64] (nseg 0) or, with ``split``, the buffer of its bf16 pieces [B * N, nseg * 3*H*64]."""
+    prep = _attention_bwd_prep_f16(out, dout, B, N, H)
+    if split:
+        return (*prep, _split_buffer(B * N, 3 * H * 64, out.device), current_segments())
+    return (*prep, torch.empty(B, N, 3 * H * 64, dtype=torch.float32, device=out.device), 0)
 
 
 def attention_bwd_f16(qkv16, out, dout, lse, B, N, H, scale, split=False, colsum=None):
@@ -947,31 +1037,16 @@ def attention_bwd_f16(qkv16, out, dout, lse, B, N, H, scale, split=False, colsum
     kernels."""
     if N > ATTN_F16_SHORT_MAX_N:
         return attention_bwd_long_f16(qkv16, out, dout, lse, B, N, H, scale, split=split, colsum=colsum)
-    dev = qkv16.device
-    dout16, delta, gscale = _attention_bwd_prep_f16(out, dout, B, N, H)
-    nseg = current_segments() if split else 0
-    dqkv = _split_buffer(B * N, 3 * H * 64, dev) if split else torch.empty(B, N, 3 * H * 64, dtype=torch.float32, device=dev)
+    dout16, delta, gscale, dqkv, nseg = _attention_bwd_start_f16(out, dout, B, N, H, split)
     check(lib().mv_attention_bwd_f16(_p(qkv16), _p(dout16), _p(delta), _p(lse), _p(gscale), _p(dqkv), nseg, _p(colsum), B, N, H,
                                      scale, _s()), "attention_bwd_f16", B=B, N=N, H=H)
     return dqkv
 
 
-def _attention_bwd_prep_f16(out, dout, B, N, H):
-    """dout fp32 -> (dout16 half scaled per (image, head) by gscale, delta = rowsum(dout16 * out), gscale fp32 [B * H])."""
-    dev = out.device
-    dout16 = torch.empty(B, N, H * 64, dtype=torch.float16, device=dev)
-    delta = torch.empty(B, H, N, dtype=torch.float32, device=dev)
-    gscale = torch.empty(B * H, dtype=torch.float32, device=dev)
-    check(lib().mv_attention_bwd_prep_f16(_p(dout), _p(out), _p(dout16), _p(delta), _p(gscale), B, N, H, _s()),
-          "attention_bwd_prep_f16", B=B, N=N, H=H)
-    return dout16, delta, gscale
-
-
 def attention_fwd_long_f16(qkv16, B, N, H, scale):
     """The key-tiled half forward (any N <= 8192): as ``attention_fwd_f16``."""
     require_cuda(qkv16)
-    out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv16.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv16.device)
+    out, lse = _attn_out(qkv16, B, N, H, torch.float32)
     check(lib().mv_attention_fwd_long_f16(_p(qkv16), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_long_f16",
           B=B, N=N, H=H)
     return out, lse
@@ -981,11 +1056,8 @@ def attention_bwd_long_f16(qkv16, out, dout, lse, B, N, H, scale, split=False, c
     """The key-tiled half backward (any N <= 8192): as ``attention_bwd_f16``.  With ``colsum`` the per-block column-sum workspace
     [B, ceil(N / 128), 3*H*64] is a torch allocation, like the prep outputs (graph capture)."""
     require_cuda(qkv16, out, dout, lse)
-    dev = qkv16.device
-    dout16, delta, gscale = _attention_bwd_prep_f16(out, dout, B, N, H)
-    nseg = current_segments() if split else 0
-    dqkv = _split_buffer(B * N, 3 * H * 64, dev) if split else torch.empty(B, N, 3 * H * 64, dtype=torch.float32, device=dev)
-    ws = torch.empty(B, (N + 127) // 128, 3 * H * 64, dtype=torch.float32, device=dev) if colsum is not None else None
+    dout16, delta, gscale, dqkv, nseg = _attention_bwd_start_f16(out, dout, B, N, H, split)
+    ws = torch.empty(B, (N + 127) // 128, 3 * H * 64, dtype=torch.float32, device=qkv16.device) if colsum is not None else None
     check(lib().mv_attention_bwd_long_f16(_p(qkv16), _p(dout16), _p(delta), _p(lse), _p(gscale), _p(dqkv), nseg, _p(colsum),
                                           _p(ws), B, N, H, scale, _s()), "attention_bwd_long_f16", B=B, N=N, H=H)
     return dqkv
@@ -1008,8 +1080,7 @@ def attention_fwd_f32_lse(qkv, B, N, H, scale):
     if N > ATTN_F32_SHORT_MAX_N:
         return attention_fwd_long_f32(qkv, B, N, H, scale)
     require_cuda(qkv)
-    out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    out, lse = _attn_out(qkv, B, N, H, torch.float32)
     check(lib().mv_attention_fwd_f32_lse(_p(qkv), _p(out), _p(lse), B, N, H, scale, _s()), "attention_fwd_f32_lse",
           B=B, N=N, H=H)
     return out, lse
@@ -1030,7 +1101,7 @@ def attention_fwd_long_f32(qkv, B, N, H, scale, lse=True):
     as ``attention_fwd_f32``)."""
     require_cuda(qkv)
     out = torch.empty(B, N, H * 64, dtype=torch.float32, device=qkv.device)
-    lse_t = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device) if lse else None
+    lse_t = _attn_rows(qkv, B, N, H) if lse else None
     check(lib().mv_attention_fwd_long_f32(_p(qkv), _p(out), _p(lse_t), B, N, H, scale, _s()), "attention_fwd_long_f32",
           B=B, N=N, H=H)
     return (out, lse_t) if lse else out
@@ -1040,11 +1111,31 @@ def attention_bwd_long_f32(qkv, out, dout, lse, B, N, H, scale):
     """The key-tiled exact-fp32 backward (any N <= 8192): as ``attention_bwd_f32_fused``; the delta workspace is a torch
     allocation (graph capture)."""
     require_cuda(qkv, out, dout, lse)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    dqkv, delta = torch.empty_like(qkv), _attn_rows(qkv, B, N, H)
     check(lib().mv_attention_bwd_long_f32(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, N, H, scale, _s()),
           "attention_bwd_long_f32", B=B, N=N, H=H)
     return dqkv
+
+
+def attention_fwd_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point):
+    """Exact fp32 attention core whose output goes straight into a quint8 quantiser: -> int8 codes [B, N, H*64].  N > 272 takes
+    the key-tiled kernel."""
+    if N > ATTN_F32_SHORT_MAX_N:
+        return attention_fwd_long_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point)
+    require_cuda(qkv)
+    codes = torch.empty(B, N, H * 64, dtype=torch.int8, device=qkv.device)
+    check(lib().mv_attention_fwd_f32_q8(_p(qkv), _p(codes), B, N, H, scale, float(q_scale), int(q_zero_point), _s()),
+          "attention_fwd_f32_q8", B=B, N=N, H=H)
+    return codes
+
+
+def attention_fwd_long_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point):
+    """The key-tiled form of ``attention_fwd_f32_q8`` (any N <= 8192)."""
+    require_cuda(qkv)
+    codes = torch.empty(B, N, H * 64, dtype=torch.int8, device=qkv.device)
+    check(lib().mv_attention_fwd_long_f32_q8(_p(qkv), _p(codes), B, N, H, scale, float(q_scale), int(q_zero_point), _s()),
+          "attention_fwd_long_f32_q8", B=B, N=N, H=H)
+    return codes
 
 
 def attention_probs_fp32(qkv, B, N, H, dh, scale):
@@ -1309,27 +1400,6 @@ def layernorm_q8(x, ldx, rows, dim, gamma, beta, eps, scale, zero_point):
     codes = torch.empty(rows, dim, dtype=torch.int8, device=x.device)
     check(lib().mv_layernorm_fwd_q8(_p(x), ldx, _p(gamma), _p(beta), _p(codes), rows, dim, float(eps), float(scale),
                                     int(zero_point), _s()), "layernorm_fwd_q8", rows=rows, dim=dim)
-    return codes
-
-
-def attention_fwd_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point):
-    """Exact fp32 attention core whose output goes straight into a quint8 quantiser: -> int8 codes [B, N, H*64].  N > 272 takes
-    the key-tiled kernel."""
-    if N > ATTN_F32_SHORT_MAX_N:
-        return attention_fwd_long_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point)
-    require_cuda(qkv)
-    codes = torch.empty(B, N, H * 64, dtype=torch.int8, device=qkv.device)
-    check(lib().mv_attention_fwd_f32_q8(_p(qkv), _p(codes), B, N, H, scale, float(q_scale), int(q_zero_point), _s()),
-          "attention_fwd_f32_q8", B=B, N=N, H=H)
-    return codes
-
-
-def attention_fwd_long_f32_q8(qkv, B, N, H, scale, q_scale, q_zero_point):
-    """The key-tiled form of ``attention_fwd_f32_q8`` (any N <= 8192)."""
-    require_cuda(qkv)
-    codes = torch.empty(B, N, H * 64, dtype=torch.int8, device=qkv.device)
-    check(lib().mv_attention_fwd_long_f32_q8(_p(qkv), _p(codes), B, N, H, scale, float(q_scale), int(q_zero_point), _s()),
-          "attention_fwd_long_f32_q8", B=B, N=N, H=H)
     return codes
 
 
