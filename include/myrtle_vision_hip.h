@@ -497,6 +497,20 @@ int mv_image_resize_u8(const uint8_t* src, long img_stride, int Hs, int Ws, cons
                        mv_stream_t stream);
 int mv_mask_resize_u8(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* yi, const int32_t* xi, uint8_t* out,
                       int B, int out_h, int out_w, mv_stream_t stream);
+/* ragged batches (detection/train.py: transforms/detection.py from_config + nested_tensor_from_tensor_list): sample b has its own
+ * output extent ext[b] = (oh_b, ow_b) <= (out_h, out_w), int32 [B, 2], inside one padded batch.  Tables as above but padded to
+ * out_w / out_h rows per sample (rows past the extent are not read); a horizontal flip is folded into the horizontal tables by
+ * the host (taps reversed), so there is no flip argument.  out fp32 [B, 3, out_h, out_w]: the normalised image on the extent and
+ * exactly 0.0 elsewhere (the reference pads after Normalize); pad_mask uint8 (bool) [B, out_h, out_w]: 0 on the extent, 1 on the
+ * padding.  Every element of both is written by the one launch.  _u8: the intermediate uint8 [B, out_h, out_w, 3] frame of a
+ * two-resampling chain (PreRandomResize -> RandomSizeCrop -> PostRandomResize), zeros outside the extent. */
+int mv_image_prepare_ragged(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* kh, const int32_t* bh,
+                            const int32_t* kv, const int32_t* bv, int ks, const int32_t* ext, float mean0, float mean1,
+                            float mean2, float std0, float std1, float std2, float* out, uint8_t* pad_mask, int B, int out_h,
+                            int out_w, mv_stream_t stream);
+int mv_image_resize_u8_ragged(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* kh, const int32_t* bh,
+                              const int32_t* kv, const int32_t* bv, int ks, const int32_t* ext, uint8_t* out, int B, int out_h,
+                              int out_w, mv_stream_t stream);
 
 /* ---- optimizer: AdamW step (timm create_optimizer 'adamw' -> torch.optim.AdamW), classification/train.py:161-166,274-277 ----
  * flat fp32 arrays of n elements; decoupled weight decay; bias corrections passed in (host computes from step) */

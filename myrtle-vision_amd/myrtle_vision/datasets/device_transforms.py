@@ -13,6 +13,10 @@ resize + flip + ToTensor + Normalize for the whole batch, bit-exact to the Pillo
 [CenterCrop] -> [RandomHorizontalFlip] -> ToTensor -> [Normalize].  Resize FOLLOWED BY RandomResizedCrop (the
 segmentation training config) is two resamplings, each rounded to uint8 by Pillow: the GPU runs them as two kernels
 (``mv_image_resize_u8`` / ``mv_mask_resize_u8`` keep the intermediate uint8 image), with a second set of tables.
+
+Detection (``DetectionDevicePlan``) differs in one way: every image leaves its chain with its own size and the batch is the
+zero-padded stack of them.  ``mv_image_prepare_ragged`` / ``mv_image_resize_u8_ragged`` take per-sample extents and write the
+padding and the padding mask themselves.
 """
 import math
 import random
@@ -209,3 +213,207 @@ class DevicePlan:
         if mask is not None:
             masks = ops.mask_prepare(mask, d["yi"], d["xi"], d["flip"], mask_add)
         return imgs, masks
+
+
+# ---- detection: ragged batches ------------------------------------------------------------------------------------------
+def _identity_axis(index):
+    """Tables that copy: one tap of weight 1.0 on source pixel ``index[x]`` (the kernel's arithmetic returns the pixel itself)."""
+    b = np.stack([index, np.ones_like(index)], axis=1).astype(np.int32)
+    return b, np.full((len(index), 1), 1 << PRECISION_BITS, np.int32)
+
+
+class TableFrame:
+    """Stands in for the PIL image inside ``detection_transforms``' chain on the worker: it has the members that chain uses
+    (``size`` / ``width`` / ``height``, ``crop``, ``transpose``, ``resize``) and, instead of touching pixels, records per axis
+    how the current image is obtained from the last MATERIALISED uint8 image -- the decoded frame, or the result of an
+    earlier resize, because Pillow rounds every resize to uint8 and a second one must start from that image.
+
+    Before a resize the current image is a window of the materialised one, possibly mirrored: the index arrays ``gx`` / ``gy``.
+    ``resize`` turns them into Pillow's resampling tables over that window (offsets folded into the bounds; a mirrored window
+    reverses each row's taps, which leaves the integer sum unchanged).  After it, ``crop`` slices table rows and a flip
+    reverses the row order.  A second ``resize`` closes the stage (``stages``) and starts over on its result."""
+
+    def __init__(self, frame, tables=None):
+        self.frame = frame                                     # uint8 [H, W, 3], the decoded image
+        self.stages = []                                       # closed stages: (bv, kv, bh, kh)
+        self.cur = None                                        # tables of the open stage, once it has resampled
+        self.gy, self.gx = np.arange(frame.shape[0]), np.arange(frame.shape[1])
+        self.norm = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+        self._tables = tables if tables is not None else bilinear_tables
+
+    @property
+    def height(self):
+        return len(self.gy) if self.cur is None else len(self.cur[0])
+
+    @property
+    def width(self):
+        return len(self.gx) if self.cur is None else len(self.cur[2])
+
+    @property
+    def size(self):
+        return self.width, self.height
+
+    def crop(self, box):
+        left, top, right, bottom = box
+        if not (0 <= left < right <= self.width and 0 <= top < bottom <= self.height):
+            raise ValueError(f"crop box {box} outside the {self.size} image")
+        if self.cur is None:
+            self.gy, self.gx = self.gy[top:bottom], self.gx[left:right]
+        else:
+            bv, kv, bh, kh = self.cur
+            self.cur = (bv[top:bottom], kv[top:bottom], bh[left:right], kh[left:right])
+        return self
+
+    def transpose(self, method):
+        from PIL import Image
+        if method != Image.Transpose.FLIP_LEFT_RIGHT:
+            raise ValueError("only FLIP_LEFT_RIGHT is supported on the device path")
+        if self.cur is None:
+            self.gx = self.gx[::-1]
+        else:
+            bv, kv, bh, kh = self.cur
+            self.cur = (bv, kv, bh[::-1], kh[::-1])
+        return self
+
+    def resize(self, size, resample=None):
+        ow, oh = size
+        w, h = self.size
+        if (ow, oh) == (w, h):
+            return self                                        # Pillow returns a copy
+        if self.cur is not None:
+            self.stages.append(self.cur)
+            self.cur, self.gy, self.gx = None, np.arange(h), np.arange(w)
+        bv, kv = self._tables(h, oh)
+        bh, kh = self._tables(w, ow)
+        bv, bh = bv.copy(), bh.copy()
+        first, last = self.gx[bh[:, 0]], self.gx[bh[:, 0] + bh[:, 1] - 1]
+        if len(self.gx) > 1 and self.gx[0] > self.gx[-1]:      # mirrored window: taps run right to left in the source
+            j = bh[:, 1:2] - 1 - np.arange(kh.shape[1])[None, :]
+            kh = np.where(j >= 0, np.take_along_axis(kh, np.maximum(j, 0), axis=1), 0).astype(np.int32)
+            first = last
+        bh[:, 0] = first
+        bv[:, 0] = self.gy[bv[:, 0]]
+        self.cur = (bv, kv, bh, kh)
+        return self
+
+    def normalized(self, mean, std):
+        self.norm = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
+        return self
+
+    def finish(self):
+        """-> the sample dict: the frame, the final stage's tables and, if there was one, the first stage's."""
+        if self.cur is None:
+            bv, kv = _identity_axis(self.gy)
+            bh, kh = _identity_axis(self.gx)
+            self.cur = (bv, kv, bh, kh)
+        if len(self.stages) > 1:
+            raise ValueError("more than two resamplings in one chain are not supported on the device path")
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+        s = {"raw": torch.from_numpy(np.ascontiguousarray(self.frame))}
+        s.update(zip(("bv", "kv", "bh", "kh"), map(t, self.cur)))
+        if self.stages:
+            s.update(zip(("bv1", "kv1", "bh1", "kh1"), map(t, self.stages[0])))
+        return s
+
+
+def _pack_stage(samples, names, src_hw):
+    """Per-sample tables of one stage -> padded [B, Hmax, ks] / [B, Wmax, ks] arrays + extents.  ``src_hw[i]`` is the size of
+    the image sample i's tables address: every bound is checked against it here, on the host, before anything is launched."""
+    bvn, kvn, bhn, khn = names
+    B = len(samples)
+    oh, ow = max(s[kvn].shape[0] for s in samples), max(s[khn].shape[0] for s in samples)
+    ks = max(max(s[khn].shape[1], s[kvn].shape[1]) for s in samples)
+    if ks > MAX_TAPS:
+        raise ValueError(f"downscale factor too large for the device path ({ks} taps)")
+    kh, kv = torch.zeros(B, ow, ks, dtype=torch.int32), torch.zeros(B, oh, ks, dtype=torch.int32)
+    bh, bv = torch.zeros(B, ow, 2, dtype=torch.int32), torch.zeros(B, oh, 2, dtype=torch.int32)
+    ext = torch.zeros(B, 2, dtype=torch.int32)
+    for i, s in enumerate(samples):
+        h, w = s[kvn].shape[0], s[khn].shape[0]
+        for b, n in ((s[bvn], src_hw[i][0]), (s[bhn], src_hw[i][1])):
+            if int(b[:, 0].min()) < 0 or int((b[:, 0] + b[:, 1]).max()) > n or int(b[:, 1].min()) < 1:
+                raise ValueError("resampling table addresses pixels outside its source image")
+        kh[i, :w, :s[khn].shape[1]], kv[i, :h, :s[kvn].shape[1]] = s[khn], s[kvn]
+        bh[i, :w], bv[i, :h] = s[bhn], s[bvn]
+        ext[i, 0], ext[i, 1] = h, w
+    return {"kh": kh, "bh": bh, "kv": kv, "bv": bv, "ext": ext}
+
+
+class DetectionDevicePlan:
+    """Built from a detection ``transform_ops_*`` section.  ``plan(pil_image, target)`` (worker) runs the host chain of
+    ``detection_transforms.from_config`` on a ``TableFrame``: the same draws, the same box / label / area arithmetic by the
+    same functions, and tables instead of pixels.  ``collate`` pads frames and tables; ``apply`` runs the ragged kernels and
+    returns the ``NestedTensor`` the host ``collate_fn`` would have built."""
+
+    def __init__(self, transform_config=None, chain=None):
+        from myrtle_vision.datasets.detection_transforms import from_config
+        self.chain = chain if chain is not None else from_config(transform_config)     # ``chain``: an already built Compose
+        self._cache = {}
+
+    def _tables(self, n_in, n_out):
+        t = self._cache.get((n_in, n_out))
+        if t is None:
+            if len(self._cache) > 4096:
+                self._cache.clear()
+            t = self._cache[(n_in, n_out)] = bilinear_tables(n_in, n_out)
+        return t
+
+    def __call__(self, img, target):
+        frame = TableFrame(np.asarray(img.convert("RGB"), dtype=np.uint8).copy(), self._tables)
+        out, target = self.chain(frame, target)
+        if out is not frame:
+            raise ValueError("transform chain not supported on the device path")
+        sample = frame.finish()
+        sample["mean"], sample["std"] = frame.norm
+        return sample, target
+
+    @staticmethod
+    def collate(batch):
+        """[(sample dict, target), ...] -> (packed dict of CPU tensors, tuple of targets).  A batch may mix one- and
+        two-resampling samples (RandomSelect draws per image): a one-resampling sample then gets a copying first stage."""
+        samples, targets = [b[0] for b in batch], tuple(b[1] for b in batch)
+        B = len(samples)
+        raw_hw = [tuple(s["raw"].shape[:2]) for s in samples]
+        Hs, Ws = max(h for h, _ in raw_hw), max(w for _, w in raw_hw)
+        raw = torch.zeros(B, Hs, Ws, 3, dtype=torch.uint8)
+        for i, s in enumerate(samples):
+            raw[i, :raw_hw[i][0], :raw_hw[i][1]] = s["raw"]
+        norms = {(tuple(map(float, s["mean"])), tuple(map(float, s["std"]))) for s in samples}
+        if len(norms) != 1:                                    # the kernel takes ONE mean / std per launch
+            raise ValueError("samples of one batch must share the normalisation")
+        out = {"raw": raw, "norm": torch.tensor(list(norms.pop()), dtype=torch.float64)}
+        src_hw = raw_hw
+        if any("kh1" in s for s in samples):
+            staged = []
+            for s, (h, w) in zip(samples, raw_hw):
+                if "kh1" not in s:
+                    s = dict(s)
+                    (s["bv1"], s["kv1"]), (s["bh1"], s["kh1"]) = (tuple(map(torch.from_numpy, _identity_axis(np.arange(n))))
+                                                                    for n in (h, w))
+                staged.append(s)
+            samples = staged
+            first = _pack_stage(samples, ("bv1", "kv1", "bh1", "kh1"), raw_hw)
+            out.update({k + "1": v for k, v in first.items()})
+            src_hw = [tuple(int(v) for v in e) for e in first["ext"]]
+        out.update(_pack_stage(samples, ("bv", "kv", "bh", "kh"), src_hw))
+        return out, targets
+
+    @staticmethod
+    def output_shapes(packed):
+        """-> (images, mask, intermediate | None) shapes of ``apply`` for a packed batch."""
+        B, oh, ow = packed["kv"].shape[0], packed["kv"].shape[1], packed["kh"].shape[1]
+        first = (B, packed["kv1"].shape[1], packed["kh1"].shape[1], 3) if "kh1" in packed else None
+        return (B, 3, oh, ow), (B, oh, ow), first
+
+    def apply(self, packed, device, out=None, mask=None, stage_out=None):
+        """Packed CPU batch -> ``NestedTensor`` (images fp32 [B, 3, Hmax, Wmax], padding mask bool [B, Hmax, Wmax]) on ``device``.
+        ``out`` / ``mask`` / ``stage_out``: preallocated results and uint8 intermediate (see ``output_shapes``)."""
+        from myrtle_vision.datasets.detection_transforms import NestedTensor
+        from myrtle_vision.hip import ops
+        mean, std = (tuple(float(v) for v in row) for row in packed["norm"])
+        d = {k: v.to(device, non_blocking=True) for k, v in packed.items() if k != "norm"}
+        raw = d["raw"]
+        if "kh1" in d:
+            raw = ops.image_resize_u8_ragged(raw, d["kh1"], d["bh1"], d["kv1"], d["bv1"], d["ext1"], out=stage_out)
+        imgs, mask = ops.image_prepare_ragged(raw, d["kh"], d["bh"], d["kv"], d["bv"], d["ext"], mean, std, out=out, mask=mask)
+        return NestedTensor(imgs, mask)

@@ -1,4 +1,4 @@
-"""Training / evaluation loops shared by ``classification/`` and ``segmentation/`` scripts.
+"""Training / evaluation loops shared by the ``classification/``, ``segmentation/`` and ``detection/`` scripts.
 
 Loop semantics follow the reference scripts (classification/train.py:55-313, segmentation/train.py, */test.py):
 seeding, batch-size solver, one process per GPU, rank-0 checkpoints every ``iters_per_checkpoint`` iterations named
@@ -17,6 +17,10 @@ seeding, batch-size solver, one process per GPU, rank-0 checkpoints every ``iter
   (``AdamW.clip_accumulated``), the last one rides into the AdamW kernel as a device scalar;
 * ``pretrained_backbone`` must be a local timm-format state dict (no network); a bare timm model NAME that is not a
   file means "random init" with a warning.
+
+``task="detection"`` follows detection/train.py:40-332 instead (``_train_detection``): padded batches of differently sized
+images, ``SetCriterion`` weighted by ``train_config``'s ``weight_dict`` keys, validation on EVERY rank once per epoch
+(``PostProcess`` -> ``CocoEvaluator`` -> validation loss) and a checkpoint ``vit_epoch{N}`` whenever AP@[.5:.95] does not drop.
 """
 import os
 import random
@@ -43,16 +47,19 @@ class ShardSampler(Sampler):
     to a multiple of the world size by repeating the head of the list, rank r takes ``indices[r::world]``
     (``tests/test_host_cpu.py::test_shard_sampler_is_torch_distributed_sampler``)."""
 
-    def __init__(self, n, rank, world, seed=0):
-        self.n, self.rank, self.world, self.seed, self.epoch = n, rank, world, seed, 0
+    def __init__(self, n, rank, world, seed=0, shuffle=True):
+        self.n, self.rank, self.world, self.seed, self.epoch, self.shuffle = n, rank, world, seed, 0, shuffle
         self.num_samples = (n + world - 1) // world
 
     def set_epoch(self, epoch):
         self.epoch = epoch
 
     def __iter__(self):
-        g = torch.Generator().manual_seed(self.seed + self.epoch)
-        idx = torch.randperm(self.n, generator=g).tolist()
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch)
+            idx = torch.randperm(self.n, generator=g).tolist()
+        else:                                                  # DistributedSampler(dataset, shuffle=False): detection/train.py:159
+            idx = list(range(self.n))
         pad = self.num_samples * self.world - len(idx)
         if pad > 0:
             idx += (idx * -(-pad // len(idx)))[:pad]
@@ -63,6 +70,17 @@ class ShardSampler(Sampler):
 
 
 def _datasets(task, data_config):
+    if task == "detection":
+        from myrtle_vision.datasets.coco import CocoDetection
+        from myrtle_vision.datasets.detection_transforms import collate_fn, from_config
+
+        def mk_det(split, ops_, plan=None):
+            """``split``: "train" | "valid" | "test" (the ``<split>_images`` / ``<split>_annotations`` keys, detection/train.py:133-144)."""
+            root = data_config["dataset_path"]
+            return CocoDetection(img_folder=os.path.join(root, data_config[f"{split}_images"]),
+                                 ann_file=os.path.join(root, "annotations", data_config[f"{split}_annotations"]),
+                                 transforms=from_config(data_config[ops_]) if plan is None else None, device_plan=plan)
+        return mk_det, collate_fn
     if task == "classification":
         from myrtle_vision.datasets.resisc45 import Resisc45 as DS
         collate = None
@@ -74,14 +92,14 @@ def _datasets(task, data_config):
     return mk, collate
 
 
-def _device_plan(data_config, ops_, enabled=True):
-    """DevicePlan for a ``transform_ops_*`` section, or None (host transforms) when disabled or the chain is not one the
-    GPU path covers.  MYRTLE_VISION_DEVICE_TRANSFORMS=0 forces the host path."""
+def _device_plan(data_config, ops_, enabled=True, task=None):
+    """DevicePlan (DetectionDevicePlan for ``task="detection"``) for a ``transform_ops_*`` section, or None (host transforms)
+    when disabled or the chain is not one the GPU path covers.  MYRTLE_VISION_DEVICE_TRANSFORMS=0 forces the host path."""
     if not enabled or os.environ.get("MYRTLE_VISION_DEVICE_TRANSFORMS", "1") == "0":
         return None
-    from myrtle_vision.datasets.device_transforms import DevicePlan
+    from myrtle_vision.datasets.device_transforms import DetectionDevicePlan, DevicePlan
     try:
-        return DevicePlan(data_config[ops_])
+        return DetectionDevicePlan(data_config[ops_]) if task == "detection" else DevicePlan(data_config[ops_])
     except ValueError:
         return None
 
@@ -96,17 +114,33 @@ def _workers():
     return max(1, min(8, n - 2))
 
 
+def _tensors_in(out):
+    """Every tensor of a staged batch: (images, labels) for classification / segmentation, (NestedTensor, [target dict, ...])
+    for detection."""
+    if torch.is_tensor(out):
+        yield out
+    elif isinstance(out, dict):
+        for v in out.values():
+            yield from _tensors_in(v)
+    elif isinstance(out, (list, tuple)):
+        for v in out:
+            yield from _tensors_in(v)
+    elif hasattr(out, "decompose"):
+        yield from _tensors_in(out.decompose())
+
+
 class BatchFeed:
     """DataLoader -> (images fp32 [B,3,H,W], labels) ON THE DEVICE, for either path: host transforms (tensors are copied
     over) or a DevicePlan (uint8 frames + tables are copied over and mv_image_prepare / mv_mask_prepare finish the
-    job).  Same batches either way (tests/test_image_prep.py)."""
+    job).  Same batches either way (tests/test_image_prep.py).  ``task="detection"``: (NestedTensor [B,3,Hmax,Wmax] + padding
+    mask, list of target dicts) instead, from the host collate or from a DetectionDevicePlan (mv_image_prepare_ragged /
+    mv_image_resize_u8_ragged), same batches either way as well (tests/test_detection_data_gpu.py)."""
 
     def __init__(self, dataset, plan, task, device, collate, **loader_kw):
-        from myrtle_vision.datasets.device_transforms import DevicePlan
         self.plan, self.task, self.device = plan, task, device
         if plan is not None:
             loader_kw.setdefault("num_workers", _workers())
-            collate = DevicePlan.collate
+            collate = plan.collate
         else:
             loader_kw.setdefault("num_workers", 1)                          # classification/train.py:117
         # workers outlive the epoch: respawning them (fork + imports) costs seconds per epoch boundary, as long as ~90
@@ -118,6 +152,10 @@ class BatchFeed:
         return len(self.loader)
 
     def _to_device(self, batch):
+        if self.task == "detection":                           # (NestedTensor, list of target dicts), both on the device
+            first, targets = batch
+            imgs = first.to(self.device) if self.plan is None else self.plan.apply(first, self.device)
+            return imgs, [{k: v.to(self.device, non_blocking=True) for k, v in t.items()} for t in targets]
         if self.plan is None:
             imgs, labels = batch
             return imgs.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True)
@@ -139,9 +177,8 @@ class BatchFeed:
                 out = self._to_device(batch)
                 ready = torch.cuda.Event()
                 ready.record(side)
-            for t in out:
-                if torch.is_tensor(t):
-                    t.record_stream(main)            # allocated on the side stream, consumed on the main one
+            for t in _tensors_in(out):
+                t.record_stream(main)                # allocated on the side stream, consumed on the main one
             return out, ready
 
         it = iter(self.loader)
@@ -217,6 +254,8 @@ def validation(val_loader, device, criterion, vit, task, num_classes):
 
 
 def train_worker(rank, num_gpus, config, task="classification"):
+    if task == "detection":
+        return _train_detection(rank, num_gpus, config)
     train_config, dist_config, vit_config = config["train_config"], config["dist_config"], config["vit_config"]
     data_config = parse_config(config["data_config_path"])
     if not torch.cuda.is_available():
@@ -372,6 +411,10 @@ def evaluate(config, task, quantize=False, calib_steps=0, quantized_ckpt=False):
     load_checkpoint(model=vit, optimizer=None, lr_scheduler=None, filepath=train_config["checkpoint_path"])
     mk, collate = _datasets(task, data_config)
     dev = torch.device("cuda")
+    if task == "detection":
+        if quantize:
+            raise NotImplementedError("quantised evaluation is a classification script (classification/test_quantize.py)")
+        return _evaluate_detection(vit, mk, collate, data_config, train_config, dev)
     plan = _device_plan(data_config, "transform_ops_val", train_config.get("device_transforms", True))
     if quantize:
         if not quantized_ckpt:
@@ -420,3 +463,191 @@ def evaluate(config, task, quantize=False, calib_steps=0, quantized_ckpt=False):
         except ImportError:
             print(f"accuracy: {acc:.4f}")
     return result
+
+
+# ---- detection (detection/train.py, detection/test.py) ----------------------------------------------------------------
+_DET_WEIGHTS = ("loss_ce", "class_error", "loss_bbox", "loss_giou", "cardinality_error")
+
+
+def _weighted(losses, weight_dict):
+    return sum(losses[k] * weight_dict[k] for k in losses.keys() if k in weight_dict)
+
+
+def _random_subset(dataset, k):
+    """detection/train.py:126-146: the first k of a ``random.shuffle`` of the indices."""
+    from torch.utils.data import Subset
+    perm = list(range(len(dataset)))
+    random.shuffle(perm)
+    return Subset(dataset, perm[:k])
+
+
+class _JsonLines:
+    """The detection loop's record (the reference logs lr and AP to TensorBoard, detection/train.py:321-323): one JSON object per
+    iteration (``iteration``, ``loss``) and per epoch (``epoch``, ``loss``, ``val_loss``, ``ap``, ``lr``), floats at full precision."""
+
+    def __init__(self, path):
+        self.path = path
+
+    def write(self, **row):
+        import json
+        with open(self.path, "a") as f:
+            f.write(json.dumps(row) + "\n")
+
+
+@torch.no_grad()
+def detection_validation(coco, val_loader, criterion, weight_dict, vit, verbose=True):
+    """detection/train.py:40-71 -> (validation loss, AP@[.5:.95], the evaluator).  Runs on every rank: the criterion
+    all-reduces the box count and the evaluator gathers the per-image records."""
+    from myrtle_vision.datasets.coco_eval import CocoEvaluator
+    from myrtle_vision.models.detector import PostProcess
+    evaluator, post = CocoEvaluator(coco, ["bbox"]), PostProcess()
+    total, n = 0.0, max(len(val_loader), 1)
+    vit.eval()
+    criterion.eval()
+    for imgs, targets in val_loader:
+        outputs = vit(imgs.tensors)
+        sizes = torch.stack([t["orig_size"] for t in targets])
+        results = post(outputs, sizes)
+        evaluator.update({int(t["image_id"].item()): r for t, r in zip(targets, results)})
+        total += float(_weighted(criterion(outputs, targets), weight_dict)) / n
+    evaluator.synchronize_between_processes()
+    evaluator.accumulate()
+    evaluator.summarize(verbose)
+    vit.train()
+    criterion.train()
+    return total, float(evaluator.coco_eval["bbox"].stats[0]), evaluator
+
+
+def _train_detection(rank, num_gpus, config):
+    from myrtle_vision.datasets.coco import coco_from_dataset
+    from myrtle_vision.models.detector import SetCriterion
+    from myrtle_vision.models.matcher import HungarianMatcher
+    train_config, dist_config, vit_config = config["train_config"], config["dist_config"], config["vit_config"]
+    data_config = parse_config(config["data_config_path"])
+    if not torch.cuda.is_available():
+        raise RuntimeError("training needs an MI355X: the myrtle_vision HIP path has no CPU fallback")
+    device = torch.device("cuda", rank)
+    torch.cuda.set_device(device)
+    seed_everything(train_config["seed"])
+    world = max(num_gpus, 1)
+    batch_size, n_batch_accum = get_batch_sizes(train_config["local_batch_size"], num_gpus,
+                                                train_config["global_batch_size"], verbose=(rank == 0))
+    train_config["local_batch_size"] = batch_size
+    train_config["global_batch_size"] = batch_size * n_batch_accum * world
+    train_config["n_batch_accum"] = n_batch_accum
+    if num_gpus > 1:
+        init_distributed(rank, num_gpus, **dist_config)
+    out_dir = train_config["output_directory"]
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        print("output directory:", out_dir)
+
+    mk, collate = _datasets("detection", data_config)
+    use_dev = train_config.get("device_transforms", True)
+    plan_t = _device_plan(data_config, "transform_ops_train", use_dev, "detection")
+    plan_v = _device_plan(data_config, "transform_ops_val", use_dev, "detection")
+    trainset = mk("train", "transform_ops_train", plan_t)
+    if data_config.get("train_subset") is not None:
+        trainset = _random_subset(trainset, data_config["train_subset"])
+    valset = mk("valid", "transform_ops_val", plan_v)
+    if data_config.get("valid_subset") is not None:
+        valset = _random_subset(valset, data_config["valid_subset"])
+    sampler = ShardSampler(len(trainset), rank, world) if num_gpus > 1 else None
+    val_sampler = ShardSampler(len(valset), rank, world, shuffle=False) if num_gpus > 1 else None
+    train_loader = BatchFeed(trainset, plan_t, "detection", device, collate, shuffle=(sampler is None), sampler=sampler,
+                             batch_size=batch_size, drop_last=train_config["drop_last_batch"])
+    val_loader = BatchFeed(valset, plan_v, "detection", device, collate, sampler=val_sampler, batch_size=batch_size,
+                           drop_last=train_config["drop_last_batch"])
+
+    vit, _ = get_models(config)
+    backbone = train_config.get("pretrained_backbone")
+    if backbone is not None:
+        if isinstance(backbone, str) and os.path.exists(backbone):
+            missing = vit.load_state_dict(rename_timm_state_dict(backbone, vit_config, data_config["number_of_classes"]),
+                                          strict=False)
+            assert missing.unexpected_keys == []
+        elif rank == 0:
+            print(f"WARNING: pretrained_backbone={backbone!r} is not a local file (no network): training from random init")
+    vit = vit.to(device)
+
+    optimizer_args = get_optimizer_args(train_config)
+    optimizer = create_optimizer(optimizer_args, vit)          # leaves out vit.unused_parameter_names() (det tokens unless live)
+    lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
+    weight_dict = {k: train_config[k] for k in _DET_WEIGHTS if k in train_config}     # an absent key is left out of the sum
+    criterion = SetCriterion(data_config["number_of_classes"], matcher=HungarianMatcher(), weight_dict=weight_dict,
+                             eos_coef=train_config["eos_coef"], losses=["labels", "boxes", "cardinality"]).to(device)
+    iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer,
+                                            lr_scheduler=lr_scheduler)
+    optimizer.arena.bump_versions()
+    reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())
+    broadcast_parameters(optimizer.arena)
+    optimizer.grad_scale = reducer.grad_scale
+    optimizer.max_grad_norm = optimizer_args.clip_grad         # the clip sequence of train_worker, see there
+    clip_every = optimizer_args.clip_grad is not None and n_batch_accum > 1
+
+    vit.train()
+    criterion.train()
+    epoch_offset = max(0, int(batch_size * world * iteration / max(len(trainset), 1)))
+    if num_gpus > 1:
+        dist.barrier()
+    n_accum, top_ap = 0, 0.0
+    log = _JsonLines(os.path.join(out_dir, "train_log.jsonl")) if rank == 0 else None
+    for epoch in range(epoch_offset, train_config["epochs"]):
+        epoch_loss = 0.0
+        if sampler is not None:
+            sampler.set_epoch(epoch)
+        for imgs, targets in train_loader:                     # every batch may have a new (H, W): no captured graph here
+            if n_accum == 0:
+                optimizer.zero_grad()
+            reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
+            loss = _weighted(criterion(vit(imgs.tensors), targets), weight_dict)
+            loss.backward()
+            value = float(loss.detach())
+            epoch_loss += value / max(len(train_loader), 1)
+            n_accum += 1
+            if clip_every and n_accum < n_batch_accum:
+                reducer.finish()
+                optimizer.clip_accumulated()
+            if n_accum == n_batch_accum:
+                n_accum = 0
+                reducer.finish()
+                optimizer.step()
+                iteration += 1
+                if rank == 0:
+                    print(f"Iteration {iteration}:\tloss={value:.4f}")
+                    log.write(iteration=iteration, loss=value)
+        if rank == 0:
+            print(f"Epoch {epoch} validation...")
+        val_loss, ap, _ = detection_validation(coco_from_dataset(valset), val_loader, criterion, weight_dict, vit,
+                                               verbose=(rank == 0))
+        if ap >= top_ap and rank == 0:
+            save_checkpoint(model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler, iteration=iteration,
+                            filepath=f"{out_dir}/vit_epoch{epoch}")
+        top_ap = max(top_ap, ap)
+        lr_scheduler.step(epoch)
+        if rank == 0:
+            log.write(epoch=epoch, loss=epoch_loss, val_loss=val_loss, ap=ap, lr=optimizer.param_groups[0]["lr"])
+            print(f"Epoch : {epoch + 1} - loss : {epoch_loss:.4f} - val_loss : {val_loss:.4f} - val_acc: {ap:.4f}\n")
+    if num_gpus > 1:
+        cleanup_distributed()
+    return iteration
+
+
+def _evaluate_detection(vit, mk, collate, data_config, train_config, dev):
+    """detection/test.py:29-73: the test split through the validation chain -> COCO bbox statistics."""
+    from myrtle_vision.datasets.coco_eval import CocoEvaluator
+    from myrtle_vision.models.detector import PostProcess
+    plan = _device_plan(data_config, "transform_ops_val", train_config.get("device_transforms", True), "detection")
+    testset = mk("test", "transform_ops_val", plan)
+    loader = BatchFeed(testset, plan, "detection", dev, collate, batch_size=train_config["local_batch_size"],
+                       drop_last=train_config["drop_last_batch"])
+    evaluator, post = CocoEvaluator(testset.coco, ["bbox"]), PostProcess()
+    vit.eval()
+    for imgs, targets in loader:
+        results = post(vit(imgs.tensors), torch.stack([t["orig_size"] for t in targets]))
+        evaluator.update({int(t["image_id"].item()): r for t, r in zip(targets, results)})
+    evaluator.synchronize_between_processes()
+    evaluator.accumulate()
+    evaluator.summarize()
+    stats = [float(v) for v in evaluator.coco_eval["bbox"].stats]
+    return {"AP": stats[0], "stats": stats}

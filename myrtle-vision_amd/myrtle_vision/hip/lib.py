@@ -112,6 +112,8 @@ SIGNATURES = {
     "mv_mask_prepare": ("plii" "pp" "p" "i" "p" "iii" "p", _I),
     "mv_image_resize_u8": ("plii" "pppp" "i" "p" "iii" "p", _I),
     "mv_mask_resize_u8": ("plii" "pp" "p" "iii" "p", _I),
+    "mv_image_prepare_ragged": ("plii" "pppp" "i" "p" "ffffff" "pp" "iii" "p", _I),
+    "mv_image_resize_u8_ragged": ("plii" "pppp" "i" "p" "p" "iii" "p", _I),
     "mv_adamw": ("pppp" "l" "ffffffff" "p" "p", _I),
     "mv_adamw_dev": ("pppp" "l" "p" "fffff" "p" "p", _I),
     "mv_grad_norm_workspace_bytes": ("", _Z),

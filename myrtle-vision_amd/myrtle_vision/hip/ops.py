@@ -1623,6 +1623,46 @@ def image_resize_u8(raw, kh, bh, kv, bv):
     return out
 
 
+def _ragged_out(out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"output must be a contiguous {dtype} tensor of shape {tuple(shape)}")
+    require_cuda(out)
+    return out
+
+
+def image_prepare_ragged(raw, kh, bh, kv, bv, ext, mean, std, out=None, mask=None):
+    """uint8 [B, Hs, Ws, 3] + per-sample tables padded to [B, ow, ks] / [B, oh, ks] + extents int32 [B, 2] = (oh_b, ow_b) ->
+    (fp32 [B, 3, oh, ow], zero outside each sample's extent; bool [B, oh, ow] padding mask, True = padding).  ``out`` / ``mask``:
+    preallocated results (every element is written)."""
+    require_cuda(raw, kh, bh, kv, bv, ext)
+    B, Hs, Ws, _ = raw.shape
+    oh, ow, ks = kv.shape[1], kh.shape[1], kh.shape[2]
+    if kv.shape[2] != ks or ext.shape != (B, 2) or ext.dtype != torch.int32:
+        raise ValueError("image_prepare_ragged: tables must share the tap count and ext must be int32 [B, 2]")
+    out = _ragged_out(out, (B, 3, oh, ow), torch.float32, raw.device)
+    mask = _ragged_out(mask, (B, oh, ow), torch.bool, raw.device)
+    check(lib().mv_image_prepare_ragged(_p(raw), Hs * Ws * 3, Hs, Ws, _p(kh), _p(bh), _p(kv), _p(bv), ks, _p(ext),
+                                        mean[0], mean[1], mean[2], std[0], std[1], std[2], _p(out), _p(mask), B, oh, ow, _s()),
+          "image_prepare_ragged", B=B, Hs=Hs, Ws=Ws, oh=oh, ow=ow, ks=ks)
+    return out, mask
+
+
+def image_resize_u8_ragged(raw, kh, bh, kv, bv, ext, out=None):
+    """The uint8 intermediate of a two-resampling chain for a ragged batch -> uint8 [B, oh, ow, 3], zeros outside the extents."""
+    require_cuda(raw, kh, bh, kv, bv, ext)
+    B, Hs, Ws, _ = raw.shape
+    oh, ow, ks = kv.shape[1], kh.shape[1], kh.shape[2]
+    if kv.shape[2] != ks or ext.shape != (B, 2) or ext.dtype != torch.int32:
+        raise ValueError("image_resize_u8_ragged: tables must share the tap count and ext must be int32 [B, 2]")
+    out = _ragged_out(out, (B, oh, ow, 3), torch.uint8, raw.device)
+    check(lib().mv_image_resize_u8_ragged(_p(raw), Hs * Ws * 3, Hs, Ws, _p(kh), _p(bh), _p(kv), _p(bv), ks, _p(ext), _p(out),
+                                          B, oh, ow, _s()),
+          "image_resize_u8_ragged", B=B, Hs=Hs, Ws=Ws, oh=oh, ow=ow, ks=ks)
+    return out
+
+
 def mask_resize_u8(mask, yi, xi):
     """uint8 [B, Hs, Ws] + NEAREST index tables -> uint8 [B, oh, ow]."""
     require_cuda(mask, yi, xi)

@@ -42,6 +42,8 @@ def get_models(config, profile=False):
     }
     if vit_config.get("live_det_tokens"):
         vit_kwargs["live_det_tokens"] = True
+    if vit_config["decoder"] == "detection" and vit_config.get("num_det_tokens") is not None:
+        vit_kwargs["num_det_tokens"] = vit_config["num_det_tokens"]    # the key the reference's yolos configs carry (default 100)
     return ViT(**vit_kwargs), None
 
 
