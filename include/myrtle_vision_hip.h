@@ -450,6 +450,16 @@ int mv_det_append_bwd(const float* dout, float* dx, float* ddet, float* dpos, in
  * (torchvision's generalized_box_iou on the xyxy boxes, no epsilon).  A label outside [0, C1) gives NaN. */
 int mv_det_cost(const float* logits, const float* boxes, const int64_t* labels, const float* tboxes, const int32_t* toff,
                 float* out, float cost_class, float cost_bbox, float cost_giou, int B, int Q, int C1, mv_stream_t stream);
+/* the assignment itself, matcher.py:84-86 (scipy.optimize.linear_sum_assignment per image), on the device: one wave per image
+ * solves the rectangular minimum-cost assignment of its [Q, T_b] block of mv_det_cost's output exactly (shortest augmenting
+ * paths, Crouse 2016, fp64 duals over the fp32 costs; +inf = a forbidden pair), pairing min(Q, T_b) queries and targets.
+ * max_t: the largest T_b (host-known); Q and max_t at most 1024 (MV_ERR_UNSUPPORTED above).  match int32 [B * Q], every element
+ * written: the flat target index toff[b] + t of query q, or -1 -- what mv_det_assign reads.  status int32 [B]: 0 solved (also
+ * T_b = 0), 1 the block holds a NaN or -inf (or T_b lies outside [0, max_t]), 2 infeasible (every complete assignment needs a
+ * +inf entry); for status != 0 every match entry of that image is -1.  Deterministic: ties go to the smaller path cost, then an
+ * unassigned column, then the lower index, so the pairs equal scipy's wherever the optimum is unique. */
+int mv_det_match(const float* cost, const int32_t* toff, int32_t* match, int32_t* status, int B, int Q, int max_t,
+                 mv_stream_t stream);
 /* detector.py:48-52,82-84: per-query targets from the matching.  match int32 [n]: flat target index of query i or -1 ->
  * tgt_class int64 [n] (no_object where unmatched), tgt_box [n, 4] (zeros where unmatched). */
 int mv_det_assign(const int32_t* match, const int64_t* labels, const float* tboxes, int64_t* tgt_class, float* tgt_box, long n,

@@ -15,6 +15,8 @@
 //                 reduces the Q rows over the batch in batch order (no float atomics) into both parameters' gradients.
 //   cost        : a wave per (image, query): softmax statistics once, then lanes over that image's targets only -- the
 //                 [B*Q, sum T] matrix of the reference, of which only the per-image diagonal blocks are ever read, is not formed.
+//   match       : a wave per image solves the assignment on its cost block (shortest augmenting paths, fp64 duals), so nothing
+//                 between the transformer's output and the loss scalar waits for the host.
 //   loss fwd    : one workgroup, threads over queries, fixed-order tree sums; the per-image cardinality counts are integer
 //                 LDS atomics (exact, order-free).
 //   loss bwd    : a thread per query writes its dlogits row and dbox from the three incoming gradient scalars.
@@ -299,6 +301,146 @@ __global__ __launch_bounds__(256) void det_assign_kernel(const int32_t* __restri
   for (int k = 0; k < 4; ++k) tgt_box[i * 4 + k] = hit ? tboxes[(long)j * 4 + k] : 0.f;
 }
 
+// Rectangular minimum-cost assignment of one image's [Q, T_b] block: the shortest-augmenting-path method of
+// scipy.optimize.linear_sum_assignment (Crouse 2016), fp64 duals and path costs over the fp32 costs, in the same operation order.
+// One wave per image.  The smaller side is the rows (scipy transposes when T_b < Q); lane l owns columns l, l + 64, ...: it alone
+// reads and writes their path cost, predecessor and visited flag inside a search, so a Dijkstra step is a lane-parallel
+// relaxation of the unvisited columns, a wave arg-min and nothing else -- the two barriers per row sit around the dual update and
+// the augmentation, which cross lanes.  Arg-min order: smaller value, then an unassigned column, then the lower index
+// (deterministic; scipy's order differs, so the assignment equals scipy's wherever the optimum is unique).
+// Every loop bound comes from the sizes: nr rows, at most nc steps per search (a step visits one more column), at most nr hops
+// per augmentation; NaN and -inf are screened while the block is staged, before the solve.
+// LDS: u[nr_max] v[nc_max] sp[nc_max] (fp64) | path[nc_max] row4col[nc_max] col4row[nr_max] (int32) | visited[nc_max] (bytes) |
+// the cost block (cost_cap floats), rows unit-stride, when it fits; otherwise the block is read from global memory.
+// Known costs outside the solve, left as they are because the serial search dominates: the transposed staging (T_b < Q) divides
+// once per element and writes LDS at a stride of Q words (a 4-way bank conflict at Q = 100), and the global-memory fallback of a
+// transposed block reads at a stride of T_b floats (uncoalesced).  A tiled transpose would remove both.
+constexpr int DET_MATCH_MAX = 1024;
+constexpr int DET_MATCH_ASSIGNED = 1 << 20;      // arg-min key: assigned flag | column << 10 | the column's row
+
+__host__ __device__ inline size_t det_match_state_bytes(int nr_max, int nc_max) {
+  return ((size_t)nr_max * 12 + (size_t)nc_max * 25 + 15) & ~(size_t)15;
+}
+
+__global__ __launch_bounds__(64) void det_match_kernel(const float* __restrict__ cost, const int32_t* __restrict__ toff,
+                                                       int32_t* __restrict__ match, int32_t* __restrict__ status, int Q, int max_t,
+                                                       int nr_max, int nc_max, int cost_cap) {
+  extern __shared__ double det_match_lds[];
+  double* u = det_match_lds;                                // [nr_max] row duals
+  double* v = u + nr_max;                                   // [nc_max] column duals
+  double* sp = v + nc_max;                                  // [nc_max] shortest path cost to a column in this search
+  int* path = (int*)(sp + nc_max);                          // [nc_max] the row a column was reached from
+  int* row4col = path + nc_max;                             // [nc_max] the column's row, or -1
+  int* col4row = row4col + nc_max;                          // [nr_max] the row's column, or -1
+  unsigned char* seen = (unsigned char*)(col4row + nr_max); // [nc_max] visited in this search
+  float* cst = (float*)((char*)det_match_lds + det_match_state_bytes(nr_max, nc_max));
+
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int t0 = toff[b], nt = toff[b + 1] - t0;
+  int32_t* m = match + (long)b * Q;
+  if (nt <= 0 || nt > max_t) {                              // no targets: solved; a count outside [0, max_t]: invalid input
+    for (int q = lane; q < Q; q += 64) m[q] = -1;
+    if (lane == 0) status[b] = nt == 0 ? 0 : 1;
+    return;
+  }
+  const float* g = cost + (long)Q * t0;
+  const bool tr = nt < Q;                                   // rows = targets, columns = queries
+  const int nr = tr ? nt : Q, nc = tr ? Q : nt;
+  const int n = Q * nt;
+  const bool in_lds = n <= cost_cap;
+
+  bool bad = false;
+  for (int idx = lane; idx < n; idx += 64) {
+    const float c = g[idx];
+    bad |= !(c > -INFINITY);                                // NaN or -inf
+    if (in_lds) {
+      if (tr) {
+        const int q = idx / nt, t = idx - q * nt;
+        cst[t * Q + q] = c;
+      } else {
+        cst[idx] = c;
+      }
+    }
+  }
+  if (__any(bad)) {
+    for (int q = lane; q < Q; q += 64) m[q] = -1;
+    if (lane == 0) status[b] = 1;
+    return;
+  }
+  for (int i = lane; i < nr; i += 64) { u[i] = 0.0; col4row[i] = -1; }
+  for (int j = lane; j < nc; j += 64) { v[j] = 0.0; row4col[j] = -1; }
+  __syncthreads();
+
+  const double inf = (double)INFINITY;
+  int st = 0;
+  for (int cur = 0; cur < nr; ++cur) {
+    for (int j = lane; j < nc; j += 64) { sp[j] = inf; seen[j] = 0; }
+    double minv = 0.0;
+    int i = cur, sink = -1;
+    for (int step = 0; step < nc; ++step) {
+      const double ui = u[i];
+      double bv = inf;
+      int bk = 0x7fffffff;
+      for (int j = lane; j < nc; j += 64) {
+        if (seen[j]) continue;
+        const float c = in_lds ? cst[i * nc + j] : (tr ? g[(long)j * nt + i] : g[(long)i * nt + j]);
+        const double r = ((minv + (double)c) - ui) - v[j];
+        double s = sp[j];
+        if (r < s) { s = r; sp[j] = r; path[j] = i; }
+        const int rw = row4col[j];
+        const int k = (rw >= 0 ? (DET_MATCH_ASSIGNED | rw) : 0) | (j << 10);
+        if (s < bv || (s == bv && k < bk)) { bv = s; bk = k; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(bv, o, 64);
+        const int ok = __shfl_xor(bk, o, 64);
+        if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
+      }
+      if (!(bv < inf)) break;                               // only forbidden pairs are left: infeasible
+      minv = bv;
+      const int j = (bk >> 10) & (DET_MATCH_MAX - 1);
+      if ((j & 63) == lane) seen[j] = 1;
+      if (bk & DET_MATCH_ASSIGNED) {
+        i = bk & (DET_MATCH_MAX - 1);
+      } else {
+        sink = j;
+        break;
+      }
+    }
+    if (sink < 0) { st = 2; break; }
+    // dual update: u[cur] += minv; for the other visited rows i (= row4col of a visited column j) u[i] += minv - sp[j];
+    // for the visited columns v[j] -= minv - sp[j]
+    if (lane == 0) u[cur] += minv;
+    for (int j = lane; j < nc; j += 64) {
+      if (!seen[j]) continue;
+      const double d = minv - sp[j];
+      v[j] -= d;
+      const int r = row4col[j];
+      if (r >= 0) u[r] += d;
+    }
+    __syncthreads();
+    if (lane == 0) {                                        // augment along the predecessors back to cur
+      int j = sink;
+      for (int hop = 0; hop < nr; ++hop) {
+        const int r = path[j];
+        row4col[j] = r;
+        const int jn = col4row[r];
+        col4row[r] = j;
+        j = jn;
+        if (r == cur) break;
+      }
+    }
+    __syncthreads();
+  }
+  for (int q = lane; q < Q; q += 64) {
+    int t = -1;
+    if (st == 0) t = tr ? row4col[q] : col4row[q];
+    m[q] = t >= 0 ? t0 + t : -1;
+  }
+  if (lane == 0) status[b] = st;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- criterion
 constexpr int DET_NSTAT = 7;
 
@@ -505,6 +647,19 @@ extern "C" int mv_det_cost(const float* logits, const float* boxes, const int64_
                            int C1, mv_stream_t stream) {
   MV_REQUIRE(det_dims_ok(B, Q, C1), MV_ERR_SHAPE);
   det_cost_kernel<<<dim3(Q, B), 64, 0, S_>>>(logits, boxes, labels, tboxes, toff, out, cost_class, cost_bbox, cost_giou, Q, C1);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+extern "C" int mv_det_match(const float* cost, const int32_t* toff, int32_t* match, int32_t* status, int B, int Q, int max_t,
+                            mv_stream_t stream) {
+  MV_REQUIRE(det_dims_ok(B, Q, 2) && max_t >= 0, MV_ERR_SHAPE);
+  MV_REQUIRE(Q <= DET_MATCH_MAX && max_t <= DET_MATCH_MAX, MV_ERR_UNSUPPORTED);
+  const int nr_max = Q < max_t ? Q : max_t, nc_max = Q < max_t ? max_t : Q;
+  const size_t state = det_match_state_bytes(nr_max, nc_max);
+  size_t cap = (DET_LDS_LIMIT - state) / sizeof(float);
+  if ((size_t)Q * max_t < cap) cap = (size_t)Q * max_t;
+  det_match_kernel<<<B, 64, state + cap * sizeof(float), S_>>>(cost, toff, match, status, Q, max_t, nr_max, nc_max, (int)cap);
   MV_CHECK_LAUNCH();
   return MV_OK;
 }

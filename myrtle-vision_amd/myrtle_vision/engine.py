@@ -494,6 +494,19 @@ class _JsonLines:
             f.write(json.dumps(row) + "\n")
 
 
+def _loss_to_host(loss, criterion):
+    """The loss scalar on the host.  With the device-mode matcher (``train_config["device_matcher"]``) the solver's per-image
+    status comes along in the same copy (0, 1 and 2 are exact in fp32), so checking it adds no synchronisation and no copy of its
+    own; scipy's message is raised for an unsolved image."""
+    status = getattr(criterion, "match_status", None)
+    if status is None:
+        return float(loss.detach())
+    from myrtle_vision.models.matcher import raise_for_status
+    both = torch.cat((loss.detach().reshape(1).float(), status.float())).cpu()
+    raise_for_status(both[1:].to(torch.int32).numpy())
+    return float(both[0])
+
+
 @torch.no_grad()
 def detection_validation(coco, val_loader, criterion, weight_dict, vit, verbose=True):
     """detection/train.py:40-71 -> (validation loss, AP@[.5:.95], the evaluator).  Runs on every rank: the criterion
@@ -509,7 +522,7 @@ def detection_validation(coco, val_loader, criterion, weight_dict, vit, verbose=
         sizes = torch.stack([t["orig_size"] for t in targets])
         results = post(outputs, sizes)
         evaluator.update({int(t["image_id"].item()): r for t, r in zip(targets, results)})
-        total += float(_weighted(criterion(outputs, targets), weight_dict)) / n
+        total += _loss_to_host(_weighted(criterion(outputs, targets), weight_dict), criterion) / n
     evaluator.synchronize_between_processes()
     evaluator.accumulate()
     evaluator.summarize(verbose)
@@ -574,7 +587,9 @@ def _train_detection(rank, num_gpus, config):
     optimizer = create_optimizer(optimizer_args, vit)          # leaves out vit.unused_parameter_names() (det tokens unless live)
     lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
     weight_dict = {k: train_config[k] for k in _DET_WEIGHTS if k in train_config}     # an absent key is left out of the sum
-    criterion = SetCriterion(data_config["number_of_classes"], matcher=HungarianMatcher(), weight_dict=weight_dict,
+    # "device_matcher": the assignment in HIP (mv_det_match) instead of scipy on the host; training and validation share it
+    matcher = HungarianMatcher(assignment="device" if train_config.get("device_matcher", False) else "host")
+    criterion = SetCriterion(data_config["number_of_classes"], matcher=matcher, weight_dict=weight_dict,
                              eos_coef=train_config["eos_coef"], losses=["labels", "boxes", "cardinality"]).to(device)
     iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer,
                                             lr_scheduler=lr_scheduler)
@@ -602,7 +617,7 @@ def _train_detection(rank, num_gpus, config):
             reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
             loss = _weighted(criterion(vit(imgs.tensors), targets), weight_dict)
             loss.backward()
-            value = float(loss.detach())
+            value = _loss_to_host(loss, criterion)
             epoch_loss += value / max(len(train_loader), 1)
             n_accum += 1
             if clip_every and n_accum < n_batch_accum:

@@ -104,6 +104,7 @@ SIGNATURES = {
     "mv_det_append_fwd": ("pppp" "iiii" "p", _I),
     "mv_det_append_bwd": ("pppp" "iiii" "p", _I),
     "mv_det_cost": ("pppppp" "fff" "iii" "p", _I),
+    "mv_det_match": ("pppp" "iii" "p", _I),
     "mv_det_assign": ("ppppp" "ll" "i" "p", _I),
     "mv_det_loss_fwd": ("pppppppp" "f" "iii" "p", _I),
     "mv_det_loss_bwd": ("pppppppppppp" "f" "iii" "p", _I),

@@ -1557,6 +1557,20 @@ def det_cost(logits, boxes, labels, tboxes, toff, total, cost_class, cost_bbox, 
     return out
 
 
+DET_MATCH_MAX = 1024          # mv_det_match: the largest Q and T_b one wave's LDS state holds
+
+
+def det_match(cost, toff, B, Q, max_t):
+    """Packed cost blocks (``det_cost``) -> (match int32 [B * Q]: flat target index of every query or -1, status int32 [B]:
+    0 solved, 1 NaN / -inf in the block or a target count outside [0, ``max_t``], 2 infeasible; an image with a non-zero status has
+    -1 throughout).  ``max_t``: the largest target count.  No host copy."""
+    require_cuda(cost, toff)
+    match = torch.empty(B * Q, dtype=torch.int32, device=cost.device)
+    status = torch.empty(B, dtype=torch.int32, device=cost.device)
+    check(lib().mv_det_match(_p(cost), _p(toff), _p(match), _p(status), B, Q, max_t, _s()), "det_match", B=B, Q=Q, max_t=max_t)
+    return match, status
+
+
 def det_assign(match, labels, tboxes, B, Q, no_object):
     """match int32 [B * Q] (flat target index or -1) -> (tgt_class int64 [B, Q], tgt_box fp32 [B, Q, 4])."""
     require_cuda(match, labels, tboxes)

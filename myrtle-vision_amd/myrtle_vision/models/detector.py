@@ -32,6 +32,7 @@ class SetCriterion(nn.Module):
         self.weight_dict = weight_dict
         self.eos_coef = eos_coef
         self.losses = losses
+        self.match_status = None
         empty_weight = torch.ones(self.num_classes + 1)
         empty_weight[-1] = self.eos_coef
         self.register_buffer("empty_weight", empty_weight)
@@ -46,9 +47,14 @@ class SetCriterion(nn.Module):
             n = float(t.item())
         return max(n / get_world_size(), 1.0)
 
-    def forward(self, outputs, targets):
+    def forward(self, outputs, targets, packed=None):
         """``outputs``: {"pred_logits": [B, Q, C + 1], "pred_boxes": [B, Q, 4]}; ``targets``: a list of B dicts with
-        "labels" [T_b] and "boxes" [T_b, 4] (cx, cy, w, h, normalised).  -> {loss name: scalar} for the requested losses."""
+        "labels" [T_b] and "boxes" [T_b, 4] (cx, cy, w, h, normalised); ``packed``: the same targets already packed
+        (``PackedTargets``).  -> {loss name: scalar} for the requested losses.
+
+        With a ``HungarianMatcher(assignment="device")`` the assignment stays on the device and nothing here waits for it:
+        ``self.match_status`` then holds the solver's per-image status (int32 [B], on the device, unread; ``None`` otherwise)
+        for the caller to check where it next synchronises (``matcher.raise_for_status``)."""
         for loss in self.losses:
             assert loss in _LOSS_KEYS, f"do you really want to compute {loss} loss?"
         logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
@@ -56,19 +62,23 @@ class SetCriterion(nn.Module):
         assert len(targets) == logits.shape[0]
         B, Q, C1 = logits.shape
         dev = logits.device
-        packed = PackedTargets(targets, dev)
+        if packed is None:
+            packed = PackedTargets(targets, dev)
         plain = {k: v for k, v in outputs.items() if k != "aux_outputs"}
-        if isinstance(self.matcher, HungarianMatcher):
-            indices = self.matcher(plain, targets, packed=packed)
+        self.match_status = None
+        if isinstance(self.matcher, HungarianMatcher) and self.matcher.on_device(plain, packed):
+            match, self.match_status = self.matcher.match_device(plain, packed)
         else:
-            indices = self.matcher(plain, targets)
-
-        # query -> flat target index (or -1), built on the host from the matching and copied once
-        match = np.full(B * Q, -1, dtype=np.int32)
-        for b, (src, tgt) in enumerate(indices):
-            if len(src):
-                match[b * Q + np.asarray(src, dtype=np.int64)] = packed.offsets[b] + np.asarray(tgt, dtype=np.int64)
-        match = torch.from_numpy(match).to(dev)
+            if isinstance(self.matcher, HungarianMatcher):
+                indices = self.matcher(plain, targets, packed=packed)
+            else:
+                indices = self.matcher(plain, targets)
+            # query -> flat target index (or -1), built on the host from the matching and copied once
+            match = np.full(B * Q, -1, dtype=np.int32)
+            for b, (src, tgt) in enumerate(indices):
+                if len(src):
+                    match[b * Q + np.asarray(src, dtype=np.int64)] = packed.offsets[b] + np.asarray(tgt, dtype=np.int64)
+            match = torch.from_numpy(match).to(dev)
         tgt_class, tgt_box = ops.det_assign(match, packed.labels, packed.boxes, B, Q, self.num_classes)
 
         weight = self.empty_weight

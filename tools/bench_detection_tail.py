@@ -9,7 +9,18 @@ detector.py:41-138) with tests/detection_ref.py's box functions in place of torc
 ROUNDS rounds; reported: the best round of each arm and its spread (slowest / fastest - 1), wall clock per step including the host
 work (the matcher synchronises, so a step is one synchronised unit in both arms).
 
-    python tools/bench_detection_tail.py [--out FILE]"""
+    python tools/bench_detection_tail.py [--out FILE]
+
+--assignment host|device|both chooses where the HIP arm solves the assignment (HungarianMatcher's ``assignment``).  ``both``
+times the HIP tail with the host matcher (scipy after a copy of the cost blocks) against the same tail with the device matcher
+(mv_det_match), alternating inside every round, instead of HIP against torch: B in {2, 64} with 1..30 targets per image and
+B = 2 with 100 targets per image (the solver's longest serial chain), MATCH_ROUNDS rounds of MATCH_ITERS steps.  The ``host``
+and ``device`` arms pack the targets inside every step, as a training step does (its targets are new every time); that packing
+is host work and a pageable host-to-device copy of the offsets.  The third arm, ``device_packed``, packs them once beforehand
+(``SetCriterion.forward(..., packed=)``): the tail with no host dependency at all.
+
+--profile-case I (with --assignment both) runs PROFILE_STEPS ``device_packed`` steps of case I and nothing else: the run to put
+under ``rocprofv3 --kernel-trace --stats`` for det_match_kernel's own time."""
 import argparse
 import json
 import os
@@ -25,36 +36,39 @@ from scipy.optimize import linear_sum_assignment  # noqa: E402
 
 import detection_ref as ref  # noqa: E402
 from myrtle_vision.models.detector import SetCriterion  # noqa: E402
-from myrtle_vision.models.matcher import HungarianMatcher  # noqa: E402
+from myrtle_vision.models.matcher import HungarianMatcher, PackedTargets  # noqa: E402
 from myrtle_vision.models.vit import DetectionDecoder  # noqa: E402
 
 ROUNDS, ITERS = 3, 20
+MATCH_ROUNDS, MATCH_ITERS = 5, 500
+PROFILE_STEPS = 100
+MATCH_CASES = ((2, None), (64, None), (2, 100))       # (B, targets per image; None = 1..30)
 D, N, Q, C = 768, 197, 100, 20
 WEIGHTS = {"loss_ce": 1.0, "loss_bbox": 5.0, "loss_giou": 2.0}
 EOS = 0.1
 
 
-def make_case(B, gen):
+def make_case(B, gen, fixed_targets=None):
     x = torch.randn(B, N, D, generator=gen).cuda().requires_grad_(True)
     dec = DetectionDecoder(D, C, Q).cuda()
     targets = []
     for _ in range(B):
-        n = int(torch.randint(1, 31, (1,), generator=gen))
+        n = int(torch.randint(1, 31, (1,), generator=gen)) if fixed_targets is None else fixed_targets
         u = torch.rand(n, 4, generator=gen)
         boxes = torch.stack((0.2 + 0.6 * u[:, 0], 0.2 + 0.6 * u[:, 1], 0.05 + 0.45 * u[:, 2], 0.05 + 0.45 * u[:, 3]), -1)
         targets.append({"labels": torch.randint(0, C, (n,), generator=gen).cuda(), "boxes": boxes.cuda()})
     return x, dec, targets
 
 
-def hip_arm(x, dec, targets):
-    crit = SetCriterion(C, HungarianMatcher(), WEIGHTS, EOS, ["labels", "boxes", "cardinality"]).cuda()
+def hip_arm(x, dec, targets, assignment="host", packed=None):
+    crit = SetCriterion(C, HungarianMatcher(assignment=assignment), WEIGHTS, EOS, ["labels", "boxes", "cardinality"]).cuda()
     params = list(dec.parameters())
 
     def step():
         x.grad = None
         for p in params:
             p.grad = None
-        losses = crit(dec(x), targets)
+        losses = crit(dec(x), targets, packed=packed)
         sum(losses[k] * w for k, w in WEIGHTS.items()).backward()
         return losses
     return step
@@ -113,16 +127,75 @@ def timeit(fn, iters):
     return (time.perf_counter() - t0) / iters * 1e6          # us, wall clock
 
 
+def compare_assignments(args, dev):
+    """HIP tail, host matcher against device matcher."""
+    gen = torch.Generator().manual_seed(0)
+    rows, lines = [], []
+    for case, (B, fixed) in enumerate(MATCH_CASES):
+        x, dec, targets = make_case(B, gen, fixed)
+        arms = {k: hip_arm(x, dec, targets, k) for k in ("host", "device")}
+        arms["device_packed"] = hip_arm(x, dec, targets, "device", PackedTargets(targets, x.device))
+        if args.profile_case is not None:
+            if case == args.profile_case:
+                timeit(arms["device_packed"], PROFILE_STEPS)
+            continue
+        a = arms["host"]()
+        gx = x.grad.clone()
+        b = arms["device"]()
+        same = all(torch.equal(a[k].detach(), b[k].detach()) for k in a) and torch.equal(gx, x.grad)
+        b = arms["device_packed"]()
+        same = same and all(torch.equal(a[k].detach(), b[k].detach()) for k in a) and torch.equal(gx, x.grad)
+        times = {k: [] for k in arms}
+        for _ in range(MATCH_ROUNDS):
+            for k, fn in arms.items():                       # arms alternate inside a round
+                times[k].append(timeit(fn, MATCH_ITERS))
+        best = {k: min(v) for k, v in times.items()}
+        spread = {k: max(v) / min(v) - 1 for k, v in times.items()}
+        rec = {"B": B, "N": N, "D": D, "Q": Q, "C": C, "targets": sum(len(t["labels"]) for t in targets),
+               "max_targets": max(len(t["labels"]) for t in targets), "device": dev, "rounds": MATCH_ROUNDS, "iters": MATCH_ITERS,
+               "host_us": round(best["host"], 1), "device_us": round(best["device"], 1),
+               "device_packed_us": round(best["device_packed"], 1),
+               "host_spread": round(spread["host"], 4), "device_spread": round(spread["device"], 4),
+               "device_packed_spread": round(spread["device_packed"], 4),
+               "host_rounds_us": [round(t, 1) for t in times["host"]], "device_rounds_us": [round(t, 1) for t in times["device"]],
+               "device_packed_rounds_us": [round(t, 1) for t in times["device_packed"]],
+               "speedup": round(best["host"] / best["device"], 2), "bit_identical": bool(same)}
+        lines.append(json.dumps(rec))
+        rows.append(f"| {B:2d} | {rec['targets']:4d} | {rec['max_targets']:3d} | {best['host']:9.1f} ({100 * spread['host']:4.1f} %) | "
+                    f"{best['device']:9.1f} ({100 * spread['device']:4.1f} %) | "
+                    f"{best['device_packed']:9.1f} ({100 * spread['device_packed']:4.1f} %) | {rec['speedup']:5.2f}x | {same} |")
+        print(rows[-1], flush=True)
+    if args.profile_case is not None:
+        return
+    head = ["| B | targets | most per image | host matcher us / step (spread) | device matcher us / step (spread) | "
+            "device matcher, targets packed beforehand | host / device | same bits |", "|---|---|---|---|---|---|---|---|"]
+    text = "\n".join(head + rows) + "\n\n" + "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(f"# tools/bench_detection_tail.py --assignment both on {dev}: the HIP detection tail (decoder + matcher + criterion,\n"
+                    f"# forward and backward, from the transformer output [B, {N}, {D}] to its gradient; Q = {Q}, C = {C}) with the\n"
+                    "# assignment solved by scipy on the host after a copy of the cost blocks, against the same tail with mv_det_match\n"
+                    "# (targets packed inside every step, as a training step does, or once beforehand);\n"
+                    f"# wall clock per step ending in a device synchronise, best of {MATCH_ROUNDS} alternating rounds of {MATCH_ITERS} steps;\n"
+                    "# spread = slowest / fastest round - 1.  same bits: all five criterion values and the gradient of x.\n")
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
+    ap.add_argument("--assignment", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--profile-case", type=int, choices=range(len(MATCH_CASES)))
     args = ap.parse_args()
     dev = torch.cuda.get_device_name(0)
+    if args.assignment == "both":
+        return compare_assignments(args, dev)
     gen = torch.Generator().manual_seed(0)
     rows, lines = [], []
     for B in (2, 64):
         x, dec, targets = make_case(B, gen)
-        arms = {"hip": hip_arm(x, dec, targets), "torch": torch_arm(x, dec, targets)}
+        arms = {"hip": hip_arm(x, dec, targets, args.assignment), "torch": torch_arm(x, dec, targets)}
         a = arms["hip"]()
         gx = x.grad.clone()
         b = arms["torch"]()
