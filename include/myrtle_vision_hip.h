@@ -237,6 +237,20 @@ int mv_embed_bwd_gather(const float* dx, void* dy, int dy_dtype, float* dpos, fl
 /* gather rows 1..T-1 of every image: dst[b*(T-1)+t-1, :] = (dtype) src[b, t, :]  (dY for the patch GEMM) */
 int mv_gather_patch_rows(const float* src, void* dst, int dst_dtype, int B, int T, int D, mv_stream_t stream);
 
+/* ---- positional-embedding resize: vit.py:292-302  F.interpolate(mode="bicubic", align_corners=False) on the (1, D, sh, sw) view ----
+ * pos / dpos fp32 [1 + sh*sw, D], out / dout fp32 [1 + gh*gw, D], token-major (the reference's transposes are index arithmetic).  Row 0
+ * (the cls slot) passes through; row 1 + y*gw + x is the grid resized to (gh, gw) as torch's upsample_bicubic2d defines it: per axis
+ * src = (dst + 0.5) * (in / out) - 0.5 (not clamped), taps floor(src) - 1 .. + 2 with indices clamped to [0, in - 1], cubic-convolution
+ * weights with A = -0.75, all in fp32; four taps without antialiasing when downscaling too; bit-exact copy when the grids are equal.
+ * Taps and weights are computed inside the kernels: no table comes from the host.
+ * D % 4 == 0 and every side positive (MV_ERR_SHAPE); sh, sw, gh, gw <= 1024 each (MV_ERR_UNSUPPORTED: the backward keeps one weight per
+ * target row and column in LDS); pointers non-NULL and 16-byte aligned (MV_ERR_ALIGN).  Nothing is launched in these cases. */
+int mv_pos_resize_fwd(const float* pos, float* out, int sh, int sw, int gh, int gw, int D, mv_stream_t stream);
+/* the exact transpose: dpos[1 + q, :] (+)= sum_p R[p, q] * dout[1 + p, :], dpos[0, :] (+)= dout[0, :]; taps clamped onto a border cell all land
+ * on that cell.  accumulate != 0 adds into dpos, otherwise every row of dpos is overwritten (rows no target touches with 0).  A gather per
+ * source cell with a fixed summation order: deterministic, no atomics on floats.  Same argument checks as mv_pos_resize_fwd. */
+int mv_pos_resize_bwd(const float* dout, float* dpos, int accumulate, int sh, int sw, int gh, int gw, int D, mv_stream_t stream);
+
 /* ---- casts / layout ---- */
 /* dst (dst_dtype) = src (src_dtype), n elements */
 int mv_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, mv_stream_t stream);

@@ -436,6 +436,33 @@ def patch_embed(img, weight, bias, cls_token, pos, patch, prec):
     return _PatchEmbed.apply(img, weight, bias, cls_token, pos, patch, prec)
 
 
+class _PosResize(Function):
+    """cls slot + the (sh, sw) grid of the positional embedding bicubically resized to (gh, gw) (vit.py:292-302) -> fp32
+    [1, 1 + gh*gw, D].  The backward writes the parameter's gradient into its arena slot when it has one (``ops.grad_out``)."""
+
+    @staticmethod
+    def forward(ctx, pos, gh, gw, sh, sw):
+        ops.require_cuda(pos)
+        D = pos.shape[-1]
+        ctx.dims = (gh, gw, sh, sw, D)
+        ctx.pos_shape = pos.shape
+        ctx.param = pos if pos.is_leaf else None
+        return ops.pos_resize_fwd(ops._f32c(pos).view(1 + sh * sw, D), gh, gw, sh, sw).view(1, 1 + gh * gw, D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        gh, gw, sh, sw, D = ctx.dims
+        dpos = ops.pos_resize_bwd(_c(dout.float()).view(1 + gh * gw, D), gh, gw, param=ctx.param, sh=sh, sw=sw)
+        return dpos.view(ctx.pos_shape), None, None, None, None
+
+
+def pos_resize(pos_embedding, gh, gw, sh=14, sw=14):
+    """``pos_embedding`` [1, 1 + sh*sw, D] (or [1 + sh*sw, D]) -> [1, 1 + gh*gw, D]; needs ``ops.pos_resize_supported(D, gh, gw, sh, sw)``."""
+    if pos_embedding.shape[-2] != 1 + sh * sw:
+        raise ValueError(f"expected 1 + {sh}*{sw} rows, got {tuple(pos_embedding.shape)}")
+    return _PosResize.apply(pos_embedding, gh, gw, sh, sw)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # fused transformer blocks
 # ------------------------------------------------------------------------------------------------------------

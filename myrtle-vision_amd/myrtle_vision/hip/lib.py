@@ -70,6 +70,8 @@ SIGNATURES = {
     "mv_embed_bwd": ("ppp" "i" "iii" "p", _I),
     "mv_gather_patch_rows": ("ppi" "iii" "p", _I),
     "mv_embed_bwd_gather": ("ppi" "pp" "iii" "p", _I),
+    "mv_pos_resize_fwd": ("pp" "iiiii" "p", _I),
+    "mv_pos_resize_bwd": ("ppi" "iiiii" "p", _I),
     "mv_cast": ("pipi" "l" "p", _I),
     "mv_split3_bf16": ("plpll" "lii" "p", _I),
     "mv_split3_ex_workspace_bytes": ("li", _Z),

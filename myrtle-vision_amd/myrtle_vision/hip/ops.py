@@ -1226,6 +1226,35 @@ def embed_bwd_gather(dx, B, T, D, out_dtype, pos=None, cls_token=None):
     return dpos, dcls, dy
 
 
+POS_RESIZE_MAX_SIDE = 1024    # per side of the source and the target grid (mv_pos_resize_fwd / _bwd)
+
+
+def pos_resize_supported(D, gh, gw, sh=14, sw=14):
+    """Restates the MV_REQUIRE lines of mv_pos_resize_fwd / _bwd: D % 4 == 0, every side in 1 .. 1024."""
+    return D > 0 and D % 4 == 0 and all(0 < s <= POS_RESIZE_MAX_SIDE for s in (gh, gw, sh, sw))
+
+
+def pos_resize_fwd(pos, gh, gw, sh=14, sw=14, out=None):
+    """pos fp32 [1 + sh*sw, D] -> [1 + gh*gw, D]: the cls row as is, the (sh, sw) grid bicubically resized to (gh, gw) (vit.py:292-302)."""
+    require_cuda(pos)
+    D = pos.shape[-1]
+    if out is None:
+        out = torch.empty(1 + gh * gw, D, dtype=torch.float32, device=pos.device)
+    check(lib().mv_pos_resize_fwd(_p(pos), _p(out), sh, sw, gh, gw, D, _s()), "pos_resize_fwd", sh=sh, sw=sw, gh=gh, gw=gw, D=D)
+    return out
+
+
+def pos_resize_bwd(dout, gh, gw, param=None, sh=14, sw=14, out=None, accumulate=False):
+    """dout fp32 [1 + gh*gw, D] -> dpos [1 + sh*sw, D], the transpose of ``pos_resize_fwd``.  ``param`` (the parameter) selects the
+    gradient destination (``grad_out``); ``out`` names one explicitly, ``accumulate`` adds into it instead of overwriting."""
+    require_cuda(dout)
+    D = dout.shape[-1]
+    dpos = out if out is not None else grad_out(param, (1 + sh * sw, D), dout.device)
+    check(lib().mv_pos_resize_bwd(_p(dout), _p(dpos), int(bool(accumulate)), sh, sw, gh, gw, D, _s()), "pos_resize_bwd", sh=sh,
+          sw=sw, gh=gh, gw=gw, D=D)
+    return dpos
+
+
 def gather_patch_rows(src, B, T, D, out_dtype):
     out = torch.empty(B * (T - 1), D, dtype=out_dtype, device=src.device)
     check(lib().mv_gather_patch_rows(_p(src), _p(out), _DT[out_dtype], B, T, D, _s()), "gather_patch_rows", B=B, T=T, D=D)

@@ -452,14 +452,22 @@ class ViT(nn.Module):
         return () if self.live_det_tokens else ("pos_embedding_det", "det_tokens")
 
     # -- positional embedding (reference vit.py:292-302) ---------------------------------------------------
+    _POS_RESIZE_CACHE_GRIDS = 4      # matrices the fallback of _pos_embedding keeps (most recently used)
+
     def _pos_embedding(self, gh: int, gw: int) -> torch.Tensor:
         """cls slot + 14x14 grid bicubically resized to (gh, gw) (reference vit.py:292-302: F.interpolate(mode="bicubic",
         align_corners=False) on the (1, D, 14, 14) view).  At 224^2 the resize is the identity and the parameter is used
-        as is.  Otherwise the resize -- a fixed linear map of the 196 grid positions -- is applied as ONE small fp32
-        product with its [gh*gw, 196] matrix: torch's bicubic kernels parallelise over the 256 output pixels only and
-        loop over the 768 channels (1.3 ms forward + 2.4 ms backward per step at 256^2, 6 % of the step)."""
+        as is.  Otherwise, on the device, ``F.pos_resize`` computes the 16-tap stencil directly (mv_pos_resize_fwd / _bwd:
+        taps and weights in the kernel, nothing built on the host, nothing cached, so a training loop that meets a new
+        padded (H, W) every batch allocates only the result; the backward writes ``pos_embedding.grad`` into its arena
+        slot).  Arguments the kernels do not take (``ops.pos_resize_supported``: D % 4 != 0, a side above 1024) fall back
+        to the resize as ONE small fp32 product with its [gh*gw, 196] matrix, built on the host per grid; that path keeps
+        the ``_POS_RESIZE_CACHE_GRIDS`` = 4 most recently used matrices per model and drops the rest.  A CPU model runs
+        torch's own interpolate, as the reference does."""
         if gh == 14 and gw == 14:
             return self.pos_embedding
+        if self.pos_embedding.is_cuda and ops.pos_resize_supported(self.pos_embedding.shape[-1], gh, gw):
+            return F.pos_resize(self.pos_embedding, gh, gw)
         cls_pos, grid = self.pos_embedding[:, 0:1, :], self.pos_embedding[0, 1:, :]
         if grid.is_cuda:
             out = F.linear(self._pos_resize_matrix(gh, gw, grid.device), grid.t().contiguous(), None)   # [gh*gw, D]
@@ -471,14 +479,19 @@ class ViT(nn.Module):
 
     def _pos_resize_matrix(self, gh: int, gw: int, device) -> torch.Tensor:
         """R [gh*gw, 196] with resize(grid)[p, :] = sum_q R[p, q] grid[q, :]: torch's own bicubic weights, obtained by
-        resizing the 196 one-hot grids on the host once per (gh, gw)."""
+        resizing the 196 one-hot grids on the host per (gh, gw).  Fallback only (see ``_pos_embedding``); the cache keeps
+        the ``_POS_RESIZE_CACHE_GRIDS`` most recently used matrices."""
         cache = self.__dict__.setdefault("_pos_resize_cache", {})
         key = (gh, gw, str(device))
-        if key not in cache:
+        r = cache.pop(key, None)
+        if r is None:
             eye = torch.eye(196, dtype=torch.float32).reshape(196, 1, 14, 14)
             r = TF.interpolate(eye, size=(gh, gw), mode="bicubic", align_corners=False)
-            cache[key] = r.reshape(196, gh * gw).t().contiguous().to(device)
-        return cache[key]
+            r = r.reshape(196, gh * gw).t().contiguous().to(device)
+        cache[key] = r                                   # most recently used last
+        while len(cache) > self._POS_RESIZE_CACHE_GRIDS:
+            del cache[next(iter(cache))]
+        return r
 
     def _embed_fusable(self):
         return (_plain(self.patch_to_embedding, Linear) and self.quant_img.plain() and self.quant_cls_token.plain()
