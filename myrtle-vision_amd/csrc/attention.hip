@@ -4,7 +4,8 @@
 // ViT sequences are short (N = 197 at 224^2, 257 at 256^2) and dim_head = 64, so one workgroup owns one
 // (image, head): its whole K and V (N x 64 bf16 = 25 KB each) sit in LDS, nothing is tiled over the sequence
 // and no online-softmax rescaling is needed.  All five/two products run on v_mfma_f32_16x16x32_bf16.  Longer sequences (384^2
-// fine-tuning, 512^2 segmentation) take the key-tiled kernels further down (mv_attention_fwd_long / _bwd_long).
+// fine-tuning, 512^2 segmentation) take the key-tiled kernels of attention_tiled.hip (mv_attention_fwd_long / _bwd_long).  This file
+// holds the whole-head family only (N <= 320); attention_common.h holds the helpers the two files share.
 //
 // Orientation is chosen so computed tiles never need a transpose through LDS (cdna guide section 3,
 // "an accumulator tile as the next MFMA's operand"):
@@ -17,15 +18,12 @@
 // The k order inside such an accumulator-fed MFMA is permuted (slot 8g+j <-> row 4g+j of tile 0 | tile 1);
 // the LDS-side fragments are gathered in the same order (rows 4g+q of each 16-row tile), which is also the
 // conflict-free order for transposed reads of 128-byte rows in the sw128 image (tools/lds_bank_sim.py).
-#include "mv_common.h"
+#include "attention_common.h"
 
 #include <atomic>
 
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 
 __device__ __forceinline__ int sw128(int row, int ch) { return row * 128 + ((ch ^ (((row >> 1) & 3) << 1)) << 4); }
 // dS^T image: [key][32 queries] bf16 = 64-byte rows; the two 32-byte halves swap on rows 4..7 (mod 8)
@@ -41,63 +39,6 @@ __device__ __forceinline__ int swds(int key, int half) { return key * 64 + ((hal
 __device__ __forceinline__ int dsy(int k) { return (((k >> 1) & 1) << 2) | (((k >> 2) & 1) << 1) | (k & 1); }
 __device__ __forceinline__ int swds4(int key, int t, int gq) { return key * 64 + (((4 * t + gq) ^ dsy((key >> 1) & 7)) << 3); }
 
-__device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
-__device__ __forceinline__ bf16x4 tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, p));
-}
-__device__ __forceinline__ bf16x8 pack8(f32x4 a, f32x4 b) {
-  bf16x8 r = {(bf16_t)a[0], (bf16_t)a[1], (bf16_t)a[2], (bf16_t)a[3], (bf16_t)b[0], (bf16_t)b[1], (bf16_t)b[2], (bf16_t)b[3]};
-  return r;
-}
-__device__ __forceinline__ bf16x4 pack4(f32x4 a) {
-  bf16x4 r = {(bf16_t)a[0], (bf16_t)a[1], (bf16_t)a[2], (bf16_t)a[3]};
-  return r;
-}
-// F16 forms (round 4, precision "bf16x3"): the SAME kernels on IEEE-half operands -- 11 significand bits instead of 8, the same
-// 2-byte geometry, LDS images, fragment maps and MFMA rate (v_mfma_f32_16x16x32_f16).  Fragments stay in their bf16x8 / bf16x4
-// containers (they are only moved); what changes is the matrix instruction and every float -> element conversion.
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
-template <bool F16>
-__device__ __forceinline__ f32x4 mma32(bf16x8 a, bf16x8 b, f32x4 c, int, int, int) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <bool F16>
-__device__ __forceinline__ bf16x8 pack8t(f32x4 a, f32x4 b) {
-  if constexpr (F16) {
-    const f16x8_t r = {(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3],
-                       (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
-    return __builtin_bit_cast(bf16x8, r);
-  } else {
-    return pack8(a, b);
-  }
-}
-template <bool F16>
-__device__ __forceinline__ bf16x4 pack4t(f32x4 a) {
-  if constexpr (F16) {
-    const f16x4_t r = {(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3]};
-    return __builtin_bit_cast(bf16x4, r);
-  } else {
-    return pack4(a);
-  }
-}
-// Outputs leave as 16-byte stores: a lane holds 4 consecutive features (8 bytes) of each 16-feature tile; for an adjacent
-// tile pair v_permlane16_swap (lanes l <-> l ^ 16, same row) leaves lane group g with 8 consecutive features of tile
-// (g & 1), starting at feature 8 (g >> 1) -- a row's four lanes then cover 64 contiguous bytes per instruction instead of
-// two 32-byte pieces in two instructions (the NT epilogue's trick; partial-sector accesses are what hurt, DESIGN finding 23).
-// Must be executed by every lane of the wave.
-__device__ __forceinline__ u32x4 pair16(f32x4 a, f32x4 b) {
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  const u32x2_t pa = __builtin_bit_cast(u32x2_t, pack4(a)), pb = __builtin_bit_cast(u32x2_t, pack4(b));
-  const u32x2_t r0 = __builtin_amdgcn_permlane16_swap(pa[0], pb[0], false, false);
-  const u32x2_t r1 = __builtin_amdgcn_permlane16_swap(pa[1], pb[1], false, false);
-  return (u32x4){r0[0], r1[0], r0[1], r1[1]};
-}
-// feature offset of that vector inside the tile pair starting at tile j0: 16 (j0 + (g & 1)) + 8 (g >> 1)
-__device__ __forceinline__ int pair16_off(int j0, int g) { return 16 * (j0 + (g & 1)) + 8 * (g >> 1); }
 // Per-lane LDS offsets of the fragment reads.  Every tile base used below is a multiple of 16 rows, so the swizzle
 // term of sw128 -- a function of (row>>1)&3 -- depends on the LANE only, and every fragment address is
 // "tile + row_base*128 + lane constant (+ 2048 for the second half of a transposed fragment)".  Computing sw128() per
@@ -556,13 +497,6 @@ __global__ __launch_bounds__(256, 3) void attn_fwd13_kernel(const bf16_t* __rest
 template <int NW>
 __device__ __forceinline__ void attn_colsum_zero(float* red, int tid, int nthreads) {
   for (int i = tid; i < NW * 192; i += nthreads) red[i] = 0.f;
-}
-__device__ __forceinline__ float rowsum16(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 8, 64);
-  return v;
 }
 template <int NW>
 __device__ __forceinline__ void attn_colsum_store(const float* red, float* __restrict__ gout, long D, int tid) {
@@ -1561,568 +1495,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2p_kernel(const bf16_t* __rest
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// N > 320: key-tiled kernels (mv_attention_fwd_long / mv_attention_bwd_long), any N up to ATTN_LONG_MAX_N
-// ------------------------------------------------------------------------------------------------
-// The kernels above hold a head's whole K and V in LDS; past 320 tokens (577 at 384^2, 1 025 for 512^2 segmentation) they do not
-// fit.  Here K / V (forward, dQ) or Q / dO (dK / dV) stream through LDS in 64-row blocks, a two-stage ring filled by LDS-DMA one
-// block ahead, and nothing of size N^2 exists anywhere.  The fragment maps, the sw128 image and the orientations are those of the
-// kernels above:
-//   forward : a wave owns 32 queries (two 16-query tiles, Q fragments in registers).  Per 64-key block S^T = K Q^T (keys on
-//             accumulator rows: the row maximum over keys is in-lane plus two shuffles), a running maximum m and a lane-local
-//             running sum l per query in fp32, O^T *= exp2(m_old - m_new), O^T += V^T P^T with P rounded to bf16 (as the short
-//             kernels round it); O is divided by l and rounded once.  Keys >= N of the ragged last block are -inf.
-//   dK / dV : a wave owns 32 keys (K, V fragments and dK^T, dV^T accumulators in registers) and sweeps the query blocks: S, dP
-//             with the key on the lane, P from the saved lse, dS = P (dP - delta) scale -- the pass B of attn_bwd2p_kernel.
-//   dQ      : a wave owns 32 queries (Q, dO fragments in registers) and sweeps the key blocks: S^T, dP^T, dS^T is at once the B
-//             operand of dQ^T += K^T dS^T -- the pass A of attn_bwd2p_kernel.
-// S and dP are computed twice (seven products instead of five); in exchange every output has exactly one owner: no atomics, no
-// cross-workgroup order, bitwise reproducible.  delta = rowsum(dO * O) comes from attn_delta_long_kernel (workspace [B, H, N]),
-// the to_qkv bias-gradient column sums from attn_colsum_long_kernel: a fixed-order pass over the rounded dqkv.
-// F16 selects the matrix instruction and the P / dS rounding (mma32 / pack8t).  F16 = true is the attention core of precision
-// "bf16x3h" past 288 tokens (mv_attention_fwd_long_f16 / _bwd_long_f16), with the conventions of attn_fwd13_kernel<true> and
-// attn_bwd2p_kernel<9, true, SPLIT>: half q / k / v, fp32 out; backward on dO16 = dO * gscale (a power of two per (image, head))
-// with delta from attn_bwd_prep_f16_kernel, dS formed without the softmax scale and clamped to half's range, the scale and
-// 1 / gscale applied to the fp32 accumulators at the store (exact for gscale); SPLIT = 0 writes fp32 dqkv, SPLIT = 3 / 6 the bf16
-// pieces of exactly those values (attn_put4_f16).  Column sums: every dK / dV and dQ workgroup writes the sums of its own 128 rows
-// of the fp32 values to a workspace [B, nblk, 3 D]; attn_colsum_ws_kernel adds the nblk partials in order.
-constexpr int ATTN_LONG_MAX_N = 8192;
-constexpr int LQB = 128;     // queries per forward / dQ workgroup (4 waves x 32)
-constexpr int LKB = 128;     // keys per dK / dV workgroup (4 waves x 32)
-constexpr int LBLK = 64;     // rows per streamed LDS block
-constexpr int LSTAGE = 2 * LBLK * 128;   // one ring stage: two [64][64] bf16 sw128 images = 16 KiB
-static_assert(LQB == LKB, "the F16 column-sum workspace has one [3 D] row per 128-row block of queries and of keys");
-
-// F16 outputs of the long backward: four consecutive fp32 features v at (row = b N + token, col < 3 D) of dqkv [B N, 3 D] (SPLIT = 0),
-// or their bf16 pieces in rows of SPLIT * 3 D, segments 3 D apart (mv_split2_bf16 / mv_split3_bf16 role 0) -- attn_bwd2p_kernel's put4
-template <int SPLIT>
-__device__ __forceinline__ void attn_put4_f16(bf16_t* __restrict__ dqkv, long row, long col, long C, f32x4 v) {
-  if constexpr (SPLIT == 0) {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(dqkv) + row * C + col) = v;
-  } else {
-    bf16_t* o = dqkv + row * (SPLIT * C) + col;
-    bf16x4 p[3];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const bf16_t p0 = (bf16_t)v[e];
-      const float r1 = v[e] - (float)p0;
-      const bf16_t p1 = (bf16_t)r1;
-      p[0][e] = p0;
-      p[1][e] = p1;
-      p[2][e] = (bf16_t)(r1 - (float)p1);
-    }
-    constexpr int order[6] = {0, 0, 1, 0, 1, 2};
-#pragma unroll
-    for (int sg = 0; sg < SPLIT; ++sg) *reinterpret_cast<bf16x4*>(o + (long)sg * C) = p[order[sg]];
-  }
-}
-
-// rows row0 .. row0 + 63 of a [*, ld] bf16 tensor (64 features from src) -> a [64][64] sw128 image: 8 pieces of 8 rows, two per
-// wave; rows >= N clamped to N - 1 (masked by the caller).  The DMA is hidden from the compiler's wait bookkeeping (glds16_hidden):
-// the caller's own s_waitcnt vmcnt(0) + barrier orders it, and the transposed LDS reads of the other stage are not held behind it.
-__device__ __forceinline__ void stage_blk64(const bf16_t* src, long ld, int row0, int N, char* dst, int wave, int lane) {
-  const int prow = lane >> 3, pch = lane & 7;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int pc = wave + 4 * i;
-    const int row = 8 * pc + prow, gr = row0 + row;
-    const long rr = gr < N ? gr : N - 1;
-    glds16_hidden(src + rr * ld + (pch ^ (((row >> 1) & 3) << 1)) * 8, dst + pc * 1024);
-  }
-}
-
-template <bool F16 = false>
-__global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                               float* __restrict__ lse, int N, int H, int nqb, float scale_log2e) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * LSTAGE];    // stage s: K [64][64] | V [64][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
-  const LaneOff L = make_lane_off(lane);
-  const int bh = blockIdx.x / nqb, qb = blockIdx.x % nqb;
-  const int b = bh / H, h = bh % H;
-  const long D = (long)H * 64;
-  const bf16_t* base = qkv + (long)b * N * 3 * D + h * 64;
-  const int nkb = (N + LBLK - 1) / LBLK;
-  auto stage = [&](int kb) __attribute__((always_inline)) {
-    char* s = smem + (kb & 1) * LSTAGE;
-    stage_blk64(base + D, 3 * D, kb * LBLK, N, s, wave, lane);
-    stage_blk64(base + 2 * D, 3 * D, kb * LBLK, N, s + LBLK * 128, wave, lane);
-  };
-  stage(0);
-  const int q0 = qb * LQB + 32 * wave;
-  bf16x8 qf[2][2];                                     // rows >= N clamped: never stored
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int qrow = q0 + 16 * t + (lane & 15);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-      qf[t][ks] = *reinterpret_cast<const bf16x8*>(base + (long)(qrow < N ? qrow : N - 1) * 3 * D + 32 * ks + 8 * g);
-  }
-  f32x4 o[2][4];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};   // l: this lane's share of the running sum (its 4 keys per tile)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kb = 0; kb < nkb; ++kb) {
-    const char* sK = smem + (kb & 1) * LSTAGE;
-    const char* sV = sK + LBLK * 128;
-    if (kb + 1 < nkb) stage(kb + 1);                   // into the stage every wave finished reading before the last barrier
-    f32x4 st[2][4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      const bf16x8 k0 = row_frag128(sK, kt * 16, L.rf[0]), k1 = row_frag128(sK, kt * 16, L.rf[1]);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = mma32<F16>(k0, qf[t][0], acc, 0, 0, 0);
-        acc = mma32<F16>(k1, qf[t][1], acc, 0, 0, 0);
-        st[t][kt] = acc;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float mb = -INFINITY;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = kb * LBLK + kt * 16 + 4 * g + r;
-          const float v = key < N ? st[t][kt][r] * scale_log2e : -INFINITY;
-          st[t][kt][r] = v;
-          mb = fmaxf(mb, v);
-        }
-      mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-      mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-      const float mn = fmaxf(m[t], mb);                // finite: key block 0 holds key 0
-      const float alpha = __builtin_amdgcn_exp2f(m[t] - mn);   // exp2(-inf) = 0 on the first block
-      m[t] = mn;
-      float s = l[t] * alpha;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(st[t][kt][r] - mn);
-          st[t][kt][r] = p;
-          s += p;
-        }
-      l[t] = s;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) o[t][dt] *= alpha;
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const bf16x8 pf0 = pack8t<F16>(st[0][2 * u], st[0][2 * u + 1]), pf1 = pack8t<F16>(st[1][2 * u], st[1][2 * u + 1]);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 vf = tr_frag128(sV, 32 * u, L.tr[dt]);
-        o[0][dt] = mma32<F16>(vf, pf0, o[0][dt], 0, 0, 0);
-        o[1][dt] = mma32<F16>(vf, pf1, o[1][dt], 0, 0, 0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of block kb + 1 have landed
-    __syncthreads();                                   // ... everyone's, and nobody reads stage kb & 1 any more
-  }
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    float s = l[t];
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[t][dt] *= inv;
-    const int qrow = q0 + 16 * t + (lane & 15);
-    if constexpr (F16) {                               // fp32 output: the lane's four features of each 16-feature tile
-      if (qrow < N) {
-        float* orow = reinterpret_cast<float*>(out) + ((long)b * N + qrow) * D + h * 64;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(orow + 16 * dt + 4 * g) = o[t][dt];
-        if (g == 0) lse[((long)b * H + h) * N + qrow] = (m[t] + __builtin_amdgcn_logf(s)) * LN2;
-      }
-    } else {
-    const u32x4 w0 = pair16(o[t][0], o[t][1]), w1 = pair16(o[t][2], o[t][3]);     // every lane (lane exchange)
-    if (qrow < N) {
-      bf16_t* orow = out + ((long)b * N + qrow) * D + h * 64;
-      *reinterpret_cast<u32x4*>(orow + pair16_off(0, g)) = w0;
-      *reinterpret_cast<u32x4*>(orow + pair16_off(2, g)) = w1;
-      if (g == 0) lse[((long)b * H + h) * N + qrow] = (m[t] + __builtin_amdgcn_logf(s)) * LN2;
-    }
-    }
-  }
-}
-
-// delta[b, h, n] = sum_d dO[b, n, h, d] O[b, n, h, d] in fp32: 8 consecutive threads per (token, head), a fixed shuffle tree
-__global__ __launch_bounds__(256) void attn_delta_long_kernel(const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
-                                                              float* __restrict__ delta, long rows, int N, int H) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;     // = ((b N + n) H + h) 8 + chunk
-  const long rh = idx >> 3;
-  float d = 0.f;
-  if (rh < rows) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(dout + idx * 8), o = *reinterpret_cast<const bf16x8*>(out + idx * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) d += (float)a[e] * (float)o[e];
-  }
-  d += __shfl_xor(d, 1, 64);
-  d += __shfl_xor(d, 2, 64);
-  d += __shfl_xor(d, 4, 64);
-  if (rh < rows && (idx & 7) == 0) {
-    const long bn = rh / H;
-    const int h = (int)(rh % H);
-    const long b = bn / N, n = bn % N;
-    delta[(b * H + h) * N + n] = d;
-  }
-}
-
-template <bool F16 = false, int SPLIT = 0>   // F16: dout = dO16 (scaled by gscale), dqkv fp32 or SPLIT pieces, colsum_ws partials
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
-                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                    bf16_t* __restrict__ dqkv, int N, int H, int nkb, float scale,
-                                                                    const float* __restrict__ gscale = nullptr,
-                                                                    float* __restrict__ colsum_ws = nullptr) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * LSTAGE];    // stage s: Q [64][64] | dO [64][64]
-  __shared__ __attribute__((aligned(16))) float sRow[2][2][LBLK];    // stage s: lse * log2(e) (+inf past N) | delta (0 past N)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
-  const LaneOff L = make_lane_off(lane);
-  const int bh = blockIdx.x / nkb, kblk = blockIdx.x % nkb;
-  const int b = bh / H, h = bh % H;
-  const long D = (long)H * 64;
-  const bf16_t* base = qkv + (long)b * N * 3 * D + h * 64;
-  const bf16_t* dobase = dout + (long)b * N * D + h * 64;
-  bf16_t* dbase = dqkv + (long)b * N * 3 * D + h * 64;
-  const float* lrow = lse + ((long)b * H + h) * N;
-  const float* drow = delta + ((long)b * H + h) * N;
-  const float c2 = scale * LOG2E;
-  const int nqb = (N + LBLK - 1) / LBLK;
-  auto stage = [&](int qb) __attribute__((always_inline)) {
-    char* s = smem + (qb & 1) * LSTAGE;
-    stage_blk64(base, 3 * D, qb * LBLK, N, s, wave, lane);
-    stage_blk64(dobase, D, qb * LBLK, N, s + LBLK * 128, wave, lane);
-  };
-  // threads 0..63 carry the block's lse, 64..127 its delta (a register load one block ahead, written before the barrier)
-  auto load_row = [&](int qb) -> float {
-    const int q = qb * LBLK + (tid & 63);
-    if (tid < 64) return q < N ? lrow[q] * LOG2E : INFINITY;
-    if (tid < 128) return q < N ? drow[q] : 0.f;
-    return 0.f;
-  };
-  auto put_row = [&](int qb, float v) {
-    if (tid < 128) sRow[qb & 1][tid >> 6][tid & 63] = v;
-  };
-  stage(0);
-  put_row(0, load_row(0));
-  const int k0 = kblk * LKB + 32 * wave;
-  const bool active = k0 < N;                          // wave-uniform; an idle wave still takes part in staging and barriers
-  bf16x8 kf[2][2], vf[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int krow = k0 + 16 * i + (lane & 15);
-    const long rr = krow < N ? krow : N - 1;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      kf[i][ks] = *reinterpret_cast<const bf16x8*>(base + rr * 3 * D + D + 32 * ks + 8 * g);
-      vf[i][ks] = *reinterpret_cast<const bf16x8*>(base + rr * 3 * D + 2 * D + 32 * ks + 8 * g);
-    }
-  }
-  f32x4 adk[2][4], adv[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      adk[i][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      adv[i][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int qb = 0; qb < nqb; ++qb) {
-    const char* sQ = smem + (qb & 1) * LSTAGE;
-    const char* sDO = sQ + LBLK * 128;
-    const float* sL = sRow[qb & 1][0];
-    const float* sD = sRow[qb & 1][1];
-    float nrow = 0.f;
-    if (qb + 1 < nqb) {
-      stage(qb + 1);
-      nrow = load_row(qb + 1);
-    }
-    if (active) {
-#pragma unroll 1
-      for (int u = 0; u < 2; ++u) {                    // 32-query halves of the block
-        bf16x8 dotr[4], qtr[4], qrf[2][2], dorf[2][2];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          dotr[dt] = tr_frag128(sDO, 32 * u, L.tr[dt]);
-          qtr[dt] = tr_frag128(sQ, 32 * u, L.tr[dt]);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            qrf[t][ks] = row_frag128(sQ, 32 * u + 16 * t, L.rf[ks]);
-            dorf[t][ks] = row_frag128(sDO, 32 * u + 16 * t, L.rf[ks]);
-          }
-        f32x4 l2v[2], dlv[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          l2v[t] = *reinterpret_cast<const f32x4*>(sL + 32 * u + 16 * t + 4 * g);
-          dlv[t] = *reinterpret_cast<const f32x4*>(sD + 32 * u + 16 * t + 4 * g);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int key = k0 + 16 * i + (lane & 15);
-          f32x4 pp[2], ds[2];
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-              sv = mma32<F16>(qrf[t][ks], kf[i][ks], sv, 0, 0, 0);
-              dp = mma32<F16>(dorf[t][ks], vf[i][ks], dp, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float p = __builtin_amdgcn_exp2f(sv[r] * c2 - l2v[t][r]);     // queries >= N: lse = +inf -> p = 0
-              p = key < N ? p : 0.f;
-              pp[t][r] = p;
-              ds[t][r] = F16 ? __builtin_amdgcn_fmed3f(p * (dp[r] - dlv[t][r]), -65000.f, 65000.f) : p * (dp[r] - dlv[t][r]) * scale;
-            }
-          }
-          const bf16x8 pf = pack8t<F16>(pp[0], pp[1]);
-          const bf16x8 dsf = pack8t<F16>(ds[0], ds[1]);
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            adv[i][dt] = mma32<F16>(dotr[dt], pf, adv[i][dt], 0, 0, 0);
-            adk[i][dt] = mma32<F16>(qtr[dt], dsf, adk[i][dt], 0, 0, 0);
-          }
-        }
-      }
-    }
-    if (qb + 1 < nqb) put_row(qb + 1, nrow);          // the stage qb + 1 & 1 was last read before the previous barrier
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if constexpr (F16) {
-    const float inv_s = 1.0f / gscale[bh], inv_ss = inv_s * scale;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        adk[i][dt] *= inv_ss;
-        adv[i][dt] *= inv_s;
-      }
-      const int key = k0 + 16 * i + (lane & 15);
-      if (key < N) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          attn_put4_f16<SPLIT>(dqkv, (long)b * N + key, D + h * 64 + 16 * dt + 4 * g, 3 * D, adk[i][dt]);
-          attn_put4_f16<SPLIT>(dqkv, (long)b * N + key, 2 * D + h * 64 + 16 * dt + 4 * g, 3 * D, adv[i][dt]);
-        }
-      }
-    }
-    if (colsum_ws) {                                   // padded keys and idle waves: exact zeros
-      float* sCs = reinterpret_cast<float*>(smem);     // [4 waves][dK 64 | dV 64]; the ring is idle after the last barrier
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float vk = rowsum16(adk[0][dt][r] + adk[1][dt][r]), vv = rowsum16(adv[0][dt][r] + adv[1][dt][r]);
-          if ((lane & 15) == 0) {
-            sCs[wave * 128 + dt * 16 + 4 * g + r] = vk;
-            sCs[wave * 128 + 64 + dt * 16 + 4 * g + r] = vv;
-          }
-        }
-      __syncthreads();
-      if (tid < 128)
-        colsum_ws[((long)b * nkb + kblk) * 3 * D + (1 + (tid >> 6)) * D + h * 64 + (tid & 63)] =
-            ((sCs[tid] + sCs[128 + tid]) + sCs[256 + tid]) + sCs[384 + tid];
-    }
-  } else {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int key = k0 + 16 * i + (lane & 15);
-#pragma unroll
-    for (int dp = 0; dp < 4; dp += 2) {
-      const u32x4 wk = pair16(adk[i][dp], adk[i][dp + 1]), wv = pair16(adv[i][dp], adv[i][dp + 1]);
-      if (key < N) {
-        *reinterpret_cast<u32x4*>(dbase + (long)key * 3 * D + D + pair16_off(dp, g)) = wk;
-        *reinterpret_cast<u32x4*>(dbase + (long)key * 3 * D + 2 * D + pair16_off(dp, g)) = wv;
-      }
-    }
-  }
-  }
-}
-
-template <bool F16 = false, int SPLIT = 0>   // F16: as attn_bwd_dkdv_long_kernel
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
-                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                  bf16_t* __restrict__ dqkv, int N, int H, int nqb, float scale,
-                                                                  const float* __restrict__ gscale = nullptr,
-                                                                  float* __restrict__ colsum_ws = nullptr) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * LSTAGE];    // stage s: K [64][64] | V [64][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
-  const LaneOff L = make_lane_off(lane);
-  const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
-  const int b = bh / H, h = bh % H;
-  const long D = (long)H * 64;
-  const bf16_t* base = qkv + (long)b * N * 3 * D + h * 64;
-  const bf16_t* dobase = dout + (long)b * N * D + h * 64;
-  bf16_t* dbase = dqkv + (long)b * N * 3 * D + h * 64;
-  const float c2 = scale * LOG2E;
-  const int nkb = (N + LBLK - 1) / LBLK;
-  auto stage = [&](int kb) __attribute__((always_inline)) {
-    char* s = smem + (kb & 1) * LSTAGE;
-    stage_blk64(base + D, 3 * D, kb * LBLK, N, s, wave, lane);
-    stage_blk64(base + 2 * D, 3 * D, kb * LBLK, N, s + LBLK * 128, wave, lane);
-  };
-  stage(0);
-  const int q0 = qblk * LQB + 32 * wave;
-  const bool active = q0 < N;
-  bf16x8 qf[2][2], dof[2][2];
-  float l2[2], dl[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int qrow = q0 + 16 * t + (lane & 15);
-    const long rr = qrow < N ? qrow : N - 1;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      qf[t][ks] = *reinterpret_cast<const bf16x8*>(base + rr * 3 * D + 32 * ks + 8 * g);
-      dof[t][ks] = *reinterpret_cast<const bf16x8*>(dobase + rr * D + 32 * ks + 8 * g);
-    }
-    l2[t] = qrow < N ? lse[((long)b * H + h) * N + rr] * LOG2E : INFINITY;     // padded queries: p = 0, never stored
-    dl[t] = qrow < N ? delta[((long)b * H + h) * N + rr] : 0.f;
-  }
-  f32x4 dq[2][4];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dq[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kb = 0; kb < nkb; ++kb) {
-    const char* sK = smem + (kb & 1) * LSTAGE;
-    const char* sV = sK + LBLK * 128;
-    if (kb + 1 < nkb) stage(kb + 1);
-    if (active) {
-#pragma unroll 1
-      for (int u = 0; u < 2; ++u) {                    // 32-key halves of the block
-        bf16x8 kr[2][2], vr[2][2], ktr[4];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            kr[kk][ks] = row_frag128(sK, 32 * u + 16 * kk, L.rf[ks]);
-            vr[kk][ks] = row_frag128(sV, 32 * u + 16 * kk, L.rf[ks]);
-          }
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) ktr[dt] = tr_frag128(sK, 32 * u, L.tr[dt]);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          f32x4 ds[2];
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-              st = mma32<F16>(kr[kk][ks], qf[t][ks], st, 0, 0, 0);
-              dp = mma32<F16>(vr[kk][ks], dof[t][ks], dp, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int key = kb * LBLK + 32 * u + 16 * kk + 4 * g + r;
-              const float p = key < N ? __builtin_amdgcn_exp2f(st[r] * c2 - l2[t]) : 0.f;
-              ds[kk][r] = F16 ? __builtin_amdgcn_fmed3f(p * (dp[r] - dl[t]), -65000.f, 65000.f) : p * (dp[r] - dl[t]) * scale;
-            }
-          }
-          const bf16x8 dsf = pack8t<F16>(ds[0], ds[1]);
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) dq[t][dt] = mma32<F16>(ktr[dt], dsf, dq[t][dt], 0, 0, 0);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if constexpr (F16) {
-    const float inv_ss = 1.0f / gscale[bh] * scale;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) dq[t][dt] *= inv_ss;
-      const int qrow = q0 + 16 * t + (lane & 15);
-      if (qrow < N) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) attn_put4_f16<SPLIT>(dqkv, (long)b * N + qrow, h * 64 + 16 * dt + 4 * g, 3 * D, dq[t][dt]);
-      }
-    }
-    if (colsum_ws) {                                   // padded queries (lse = +inf) and idle waves: exact zeros
-      float* sCs = reinterpret_cast<float*>(smem);     // [4 waves][dQ 64]; the ring is idle after the last barrier
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float vq = rowsum16(dq[0][dt][r] + dq[1][dt][r]);
-          if ((lane & 15) == 0) sCs[wave * 64 + dt * 16 + 4 * g + r] = vq;
-        }
-      __syncthreads();
-      if (tid < 64)
-        colsum_ws[((long)b * nqb + qblk) * 3 * D + h * 64 + tid] = ((sCs[tid] + sCs[64 + tid]) + sCs[128 + tid]) + sCs[192 + tid];
-    }
-  } else {
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int qrow = q0 + 16 * t + (lane & 15);
-    const u32x4 w0 = pair16(dq[t][0], dq[t][1]), w1 = pair16(dq[t][2], dq[t][3]);
-    if (qrow < N) {
-      bf16_t* drow = dbase + (long)qrow * 3 * D;
-      *reinterpret_cast<u32x4*>(drow + pair16_off(0, g)) = w0;
-      *reinterpret_cast<u32x4*>(drow + pair16_off(2, g)) = w1;
-    }
-  }
-  }
-}
-
-// colsum[b][c] = sum_n dqkv[b, n, c] (c < 3 D) in fp32, in a fixed order: thread (phase = tid >> 5, 8 columns from 8 (tid & 31))
-// adds rows phase, phase + 8, ...; the eight phase sums are added in order.  One workgroup per (256 columns, image).
-__global__ __launch_bounds__(256) void attn_colsum_long_kernel(const bf16_t* __restrict__ dqkv, float* __restrict__ colsum, int N,
-                                                               int C) {
-  __shared__ float red[8][256];
-  const int tid = threadIdx.x, ph = tid >> 5, c8 = 8 * (tid & 31);
-  const int c = blockIdx.x * 256 + c8, b = blockIdx.y;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (c < C) {
-    const bf16_t* p = dqkv + (long)b * N * C + c;
-    for (int n = ph; n < N; n += 8) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(p + (long)n * C);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[ph][c8 + e] = acc[e];
-  __syncthreads();
-  const int cc = blockIdx.x * 256 + tid;
-  if (cc < C) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += red[k][tid];
-    colsum[(long)b * C + cc] = s;
-  }
-}
-
-// colsum[b][c] = sum_k ws[b][k][c] over the nblk row-block partials of the F16 long backward, k = 0, 1, ... in order
-__global__ __launch_bounds__(256) void attn_colsum_ws_kernel(const float* __restrict__ ws, float* __restrict__ colsum, int nblk, int C,
-                                                             long total) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;     // = b C + c
-  if (idx >= total) return;
-  const long b = idx / C, c = idx % C;
-  const float* p = ws + b * nblk * C + c;
-  float s = 0.f;
-  for (int k = 0; k < nblk; ++k) s += p[(long)k * C];
-  colsum[idx] = s;
-}
-
 template <typename K>
 int set_smem(K kernel, int bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
@@ -2355,89 +1727,6 @@ extern "C" int mv_attention_bwd(const void* qkv, const void* out, const void* do
     attn_bwd_kernel<20, 3><<<B * H, 512, bwd_smem(20), s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
                                                           lse, (bf16_t*)dqkv, colsum, N, H, scale);
   }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// any N up to ATTN_LONG_MAX_N: the key-tiled kernels (ops.attention_fwd / _bwd route N > 320 here)
-// ------------------------------------------------------------------------------------------------
-extern "C" int mv_attention_fwd_long(const void* qkv, void* out, float* lse, int B, int N, int H, float scale,
-                                     mv_stream_t stream) {
-  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && N <= ATTN_LONG_MAX_N, MV_ERR_SHAPE);
-  const long nqb = (N + LQB - 1) / LQB;
-  MV_REQUIRE(nqb * B * H < (1L << 31), MV_ERR_SHAPE);
-  MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(out) && lse, MV_ERR_ALIGN);
-  if (B == 0) return MV_OK;
-  attn_fwd_long_kernel<false><<<(unsigned)(nqb * B * H), 256, 0, (hipStream_t)stream>>>(
-      (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, (int)nqb, scale * LOG2E);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
-}
-
-extern "C" int mv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, float* delta_ws,
-                                     void* dqkv, float* colsum, int B, int N, int H, float scale, mv_stream_t stream) {
-  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && N <= ATTN_LONG_MAX_N, MV_ERR_SHAPE);
-  const long nqb = (N + LQB - 1) / LQB, nkb = (N + LKB - 1) / LKB, rows8 = (long)B * N * H * 8;
-  MV_REQUIRE(nqb * B * H < (1L << 31) && nkb * B * H < (1L << 31) && (rows8 + 255) / 256 < (1L << 31) && B < 65536,
-             MV_ERR_SHAPE);
-  MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(out) && mv_aligned16(dout) && mv_aligned16(dqkv) && lse && delta_ws, MV_ERR_ALIGN);
-  if (B == 0) return MV_OK;
-  hipStream_t s = (hipStream_t)stream;
-  attn_delta_long_kernel<<<(unsigned)((rows8 + 255) / 256), 256, 0, s>>>((const bf16_t*)out, (const bf16_t*)dout, delta_ws,
-                                                                         (long)B * N * H, N, H);
-  attn_bwd_dkdv_long_kernel<false><<<(unsigned)(nkb * B * H), 256, 0, s>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta_ws,
-                                                                          (bf16_t*)dqkv, N, H, (int)nkb, scale);
-  attn_bwd_dq_long_kernel<false><<<(unsigned)(nqb * B * H), 256, 0, s>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta_ws,
-                                                                        (bf16_t*)dqkv, N, H, (int)nqb, scale);
-  if (colsum) {
-    const int C = 3 * H * 64;
-    attn_colsum_long_kernel<<<dim3((C + 255) / 256, B), 256, 0, s>>>((const bf16_t*)dqkv, colsum, N, C);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// precision "bf16x3h" past 288 tokens: the key-tiled kernels on IEEE-half operands (ops.attention_fwd_f16 / _bwd_f16 route
-// N > 288 here); any 1 <= N <= ATTN_LONG_MAX_N
-// ------------------------------------------------------------------------------------------------
-extern "C" int mv_attention_fwd_long_f16(const void* qkv16, float* out, float* lse, int B, int N, int H, float scale,
-                                         mv_stream_t stream) {
-  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && N <= ATTN_LONG_MAX_N, MV_ERR_SHAPE);
-  const long nqb = (N + LQB - 1) / LQB;
-  MV_REQUIRE(nqb * B * H < (1L << 31), MV_ERR_SHAPE);
-  MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(out) && lse, MV_ERR_ALIGN);
-  if (B == 0) return MV_OK;
-  attn_fwd_long_kernel<true><<<(unsigned)(nqb * B * H), 256, 0, (hipStream_t)stream>>>(
-      (const bf16_t*)qkv16, (bf16_t*)out, lse, N, H, (int)nqb, scale * LOG2E);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
-}
-
-extern "C" int mv_attention_bwd_long_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse,
-                                         const float* gscale, void* dqkv, int nseg, float* colsum, float* colsum_ws, int B, int N,
-                                         int H, float scale, mv_stream_t stream) {
-  MV_REQUIRE(B >= 0 && N > 0 && H > 0 && N <= ATTN_LONG_MAX_N, MV_ERR_SHAPE);
-  MV_REQUIRE(nseg == 0 || nseg == 3 || nseg == 6, MV_ERR_UNSUPPORTED);
-  const long nb = (N + LQB - 1) / LQB, C = 3L * H * 64;
-  MV_REQUIRE(nb * B * H < (1L << 31) && ((long)B * C + 255) / 256 < (1L << 31), MV_ERR_SHAPE);
-  MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(dout16) && mv_aligned16(dqkv) && delta && lse && gscale && (!colsum || colsum_ws),
-             MV_ERR_ALIGN);
-  if (B == 0) return MV_OK;
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = colsum ? colsum_ws : nullptr;
-#define MV_BWD_LONG_F16(SPLIT_)                                                                                                 \
-  {                                                                                                                            \
-    attn_bwd_dkdv_long_kernel<true, SPLIT_><<<(unsigned)(nb * B * H), 256, 0, s>>>(                                            \
-        (const bf16_t*)qkv16, (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, (int)nb, scale, gscale, ws);             \
-    attn_bwd_dq_long_kernel<true, SPLIT_><<<(unsigned)(nb * B * H), 256, 0, s>>>(                                              \
-        (const bf16_t*)qkv16, (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, (int)nb, scale, gscale, ws);             \
-  }
-  if (nseg == 0) MV_BWD_LONG_F16(0) else if (nseg == 3) MV_BWD_LONG_F16(3) else MV_BWD_LONG_F16(6)
-#undef MV_BWD_LONG_F16
-  if (colsum)
-    attn_colsum_ws_kernel<<<(unsigned)(((long)B * C + 255) / 256), 256, 0, s>>>(ws, colsum, (int)nb, (int)C, (long)B * C);
   MV_CHECK_LAUNCH();
   return MV_OK;
 }

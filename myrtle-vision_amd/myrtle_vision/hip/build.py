@@ -15,13 +15,13 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 LIB_DIR = os.path.join(PKG_ROOT, "lib")
 LIB_PATH = os.environ.get("MV_LIB_PATH") or os.path.join(LIB_DIR, "libmyrtle_vision_hip.so")   # MV_LIB_PATH: diagnostic builds
 INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
-SOURCES = ["layernorm.hip", "gemm_bf16.hip", "gemm_f32.hip", "attention.hip", "attention_dh.hip", "attention_f32.hip", "elementwise.hip", "seg_tail.hip",
+SOURCES = ["layernorm.hip", "gemm_bf16.hip", "gemm_f32.hip", "attention.hip", "attention_tiled.hip", "attention_f32.hip", "elementwise.hip", "seg_tail.hip",
            "detection.hip", "image_prep.hip", "pos_resize.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
-# per file.  attention.hip, attention_dh.hip: their softmax arithmetic sits between MFMAs, where a packed f32 operation (what SLP
+# per file.  attention.hip, attention_tiled.hip (the whole-head and the key-tiled attention kernels): their softmax arithmetic sits between MFMAs, where a packed f32 operation (what SLP
 # vectorisation makes of adjacent scalar ones) costs more issue time than the two it replaces (MI355X_MICROARCH.md, vector-instruction
 # issue cost)
-EXTRA_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "attention_dh.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "attention_tiled.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():

@@ -215,7 +215,8 @@ def emulate(family, qkv, dout, H, rounded=True):
     P = exp2(fma(score, sl2, -fp32(lse * log2(e)))) -- four fp32 roundings at the size of the score, which is what limits the fp32
     kernels when scores reach +-200.  delta, dP and dS are fp32.
     Every product is accumulated in fp32 instruction by instruction (mm below); delta = rowsum(dO * O) is an fp32 sum.
-    bf16 / half (csrc/attention.hip): P is rounded to the operand type before P.V and P^T.dO (pack8t), dS before dS.K and dS^T.Q.  bf16: O and dqkv are rounded to bf16, delta = rowsum(dO * O) reads that rounded O, dS carries
+    bf16 / half (csrc/attention.hip): P is rounded to the operand type before P.V and P^T.dO (pack8t of
+    csrc/attention_common.h), dS before dS.K and dS^T.Q.  bf16: O and dqkv are rounded to bf16, delta = rowsum(dO * O) reads that rounded O, dS carries
     the softmax scale.  half: O stays fp32; dO is multiplied by a power of two per (image, head) and rounded to half, delta uses the
     rounded dO, dS is formed without the softmax scale (applied to the fp32 dQ / dK), the power of two is divided out at the end.
     fp32 (csrc/attention_f32.hip): nothing is rounded below fp32.

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The key-tiled bf16 attention core (N > 320) against the materialised fp32 path it replaces, ViT-B heads (H = 12), GPU.
 
-Per length, alternating in one process (best of ROUNDS): the long forward and backward (ops.attention_fwd_long / _bwd_long),
+Per length, alternating in one process (best of ROUNDS; the JSON lines also carry each arm's spread, slowest round / fastest
+round - 1): the long forward and backward (ops.attention_fwd_long / _bwd_long),
 the materialised path of functional._AttnBlock (q, k, v cast to fp32, [B, H, N, N] probabilities, the fp32 products, the
 bf16 casts) forward and backward, and at N = 257 the whole-head kernels (mv_attention_fwd / _bwd) that the long ones would
 replace there -- the price of being general.  Algorithmic FLOP: forward 4 B H N^2 64, backward 10 B H N^2 64.
@@ -129,10 +130,11 @@ def main():
         gen = torch.Generator(device="cuda").manual_seed(N)
         iters = max(3, min(50, int(2e12 / (10.0 * B * H * N * N * 64) * 20)))
         arms = half_arms(B, N, gen) if args.half else f32_arms(B, N, gen) if args.f32 else bf16_arms(B, N, gen)
-        best = {k: 1e30 for k in arms}
+        times = {k: [] for k in arms}
         for _ in range(ROUNDS):
             for k, fn in arms.items():
-                best[k] = min(best[k], timeit(fn, iters))
+                times[k].append(timeit(fn, iters))
+        best = {k: min(v) for k, v in times.items()}
         fl_f, fl_b = 4.0 * B * H * N * N * 64, 10.0 * B * H * N * N * 64
         other = "short" if N <= short_cap else "mat"
         rec = {"B": B, "N": N, "H": H, "device": dev, "iters": iters, "rounds": ROUNDS}
@@ -142,6 +144,7 @@ def main():
             rec["core"] = "fp32 (fp32, bf16x3)"
         for k, us in best.items():
             rec[k + "_us"] = round(us, 1)
+            rec[k + "_spread"] = round(max(times[k]) / us - 1, 4)      # slowest round / fastest round - 1
             if k == "prep":
                 continue
             rec[k + "_tflops"] = round((fl_f if k.endswith("fwd") else fl_b) / us / 1e6, 1)

@@ -33,7 +33,7 @@ def sw256(row, ch):          # 256-byte rows (128 bf16): image used by gemm TN t
     return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)))
 
 
-def sw_dh(dh, row, ch):      # attention_dh.hip: [64][dh] bf16 blocks, rows of 2 dh bytes (dh = 32: 64 B, dh = 128: 256 B)
+def sw_dh(dh, row, ch):      # attention_tiled.hip: [64][dh] bf16 blocks, rows of 2 dh bytes (dh = 32: 64 B, dh = 128: 256 B)
     f = ((row >> 2) & 1) << 1 if dh == 32 else (row & 7) << 1
     return 2 * dh * row + 16 * (ch ^ f)
 
@@ -85,7 +85,7 @@ def main():
         a = [sw128((l & 15), (8 * (l >> 4) + 32 * j) // 16) + (8 * (l >> 4) + 32 * j) % 16 for l in range(64)]
         cy = cycles(a, 8, HALVES, 64)
         print(f"b64 row read (k-permuted) j={j}: {cy} cycles (ideal 2)")
-    # 6. "dh" cases: attention_dh.hip's images for 32- and 128-wide heads.  Row fragments: lane -> row base+(l&15), chunk 4ks+(l>>4);
+    # 6. "dh" cases: attention_tiled.hip's images for 32- and 128-wide heads.  Row fragments: lane -> row base+(l&15), chunk 4ks+(l>>4);
     #    transposed fragments in the accumulator's k order: rows base+4g+q (and +16), chunk 2dt+(p>>1), + 8 (p&1)
     for dh in (32, 128):
         wr = wt = 0
