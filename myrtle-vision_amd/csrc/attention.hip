@@ -90,6 +90,7 @@ __device__ __forceinline__ void stage_kv_dma(const bf16_t* base, long D, int N, 
 // ------------------------------------------------------------------------------------------------
 // forward: one 256-thread workgroup per (image, head); waves take 16-query tiles round-robin
 // ------------------------------------------------------------------------------------------------
+constexpr int fwd_smem(int nkt) { return nkt * 16 * 128 * 2; }   // sK | sV (also attn_fwd2_kernel)
 template <int NKT, bool F16 = false>   // F16: half operands, fp32 output (precision "bf16x3h")
 __global__ __launch_bounds__(256, (NKT <= 18 ? 2 : 1)) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                           float* __restrict__ lse, int N, int H, float scale_log2e) {
@@ -345,6 +346,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const bf16_t* __restr
 // key tiles (six pairs + one), V sits FIRST in LDS and K behind it: the P.V product's last pair reads "V rows 208..223" out of
 // K's first 16 rows -- finite values times p = 0 exactly (keys >= N are masked to -inf before the exponential), the same
 // argument as the clamped padding rows.  3 072 workgroups then take 4 rounds of 768 instead of 6 of 512.
+constexpr int fwd13_smem = 2 * 13 * 16 * 128;   // sV | sK
 template <bool F16 = false>   // F16: half operands, fp32 output (precision "bf16x3")
 __global__ __launch_bounds__(256, 3) void attn_fwd13_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                             float* __restrict__ lse, int N, int H, float scale_log2e) {
@@ -511,6 +513,7 @@ __device__ __forceinline__ void attn_colsum_store(const float* red, float* __res
 // ------------------------------------------------------------------------------------------------
 // backward: one 512-thread workgroup per (image, head); wave w owns key tiles w, w+8, (w+16)
 // ------------------------------------------------------------------------------------------------
+constexpr int bwd_smem(int nkt) { return nkt * 16 * 128 * 2 + 2 * 8192 + 2 * nkt * 16 * 64 + 2 * nkt * 16 * 4; }   // sK | sV | sPair | sDS | lse, delta
 template <int NKT, int KPW>  // NKT 16-key tiles (even), KPW key tiles per wave
 __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                           const bf16_t* __restrict__ dout, const float* __restrict__ lse,
@@ -715,6 +718,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(const bf16_t* __restri
 // SPLIT = 3 / 6 (F16 only): dQ / dK / dV leave as the bf16 PIECES of the split-operand products (mv_split2_bf16 / mv_split3_bf16 role 0,
 // rows of SPLIT * 3 D, segments 3 D apart) instead of fp32 -- the dY operand of to_qkv's dW and dX products, without an fp32 dqkv and
 // a split pass over it (8 B per element of traffic per layer); the bias gradient comes from the kernel's own column sums.
+constexpr int bwd4_smem = 224 * 128 + 208 * 128 + 8192 + 224 * 64 + 2 * 224 * 4;   // sK | sV | sPair | sDS | lse, delta: 79,616 B
 template <int NW, bool F16 = false, int SPLIT = 0>   // waves per workgroup: 4 (256 registers per lane) or 2 (one wave per SIMD: 512)
 __global__ __launch_bounds__(64 * NW, NW / 2) void attn_bwd4_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                            const bf16_t* __restrict__ dout, const float* __restrict__ lse,
@@ -1183,6 +1187,7 @@ __device__ __forceinline__ void stage_rows_dma(const bf16_t* src, long ld, int N
 
 // F16 / SPLIT: as attn_bwd4_kernel -- half operands, dout scaled per (image, head) by gscale, delta precomputed (no O loads),
 // outputs fp32 (SPLIT = 0) or the bf16 pieces of the split-operand products (SPLIT = 3 / 6) with the scale divided out
+constexpr int bwd2p_smem(int np32) { return 2 * np32 * 32 * 128 + 2 * np32 * 32 * 4 + 4 * 192 * 4; }   // sA | sB | lse, delta | column sums
 template <int NP32, bool F16 = false, int SPLIT = 0>
 __global__ __launch_bounds__(256, 2) void attn_bwd2p_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                             const bf16_t* __restrict__ dout, const float* __restrict__ lse,
@@ -1495,23 +1500,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2p_kernel(const bf16_t* __rest
   }
 }
 
-template <typename K>
-int set_smem(K kernel, int bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
-                 hipSuccess
-             ? 0
-             : -1;
-}
-
-constexpr int fwd_smem(int nkt) { return nkt * 16 * 128 * 2; }
-constexpr int bwd_smem(int nkt) { return nkt * 16 * 128 * 2 + 2 * 8192 + 2 * nkt * 16 * 64 + 2 * nkt * 16 * 4; }
-
-}  // namespace
-
-namespace {
 std::atomic<int> g_bwd_variant{0};
 std::atomic<int> g_fwd_variant{getenv("MV_ATTN_FWD") ? atoi(getenv("MV_ATTN_FWD")) : 0};   // 0 auto | 1 one query tile per wave pass | 2 pairs
-}
+}  // namespace
+
 extern "C" int mv_attention_fwd_force(int variant) {
   if (variant != 0 && variant != 1 && variant != 2 && variant != 3) return MV_ERR_UNSUPPORTED;
   g_fwd_variant.store(variant, std::memory_order_relaxed);
@@ -1531,30 +1523,16 @@ extern "C" int mv_attention_fwd(const void* qkv, void* out, float* lse, int B, i
   hipStream_t s = (hipStream_t)stream;
   const float sl = scale * LOG2E;
   const int fv = g_fwd_variant.load(std::memory_order_relaxed);
-  if (N <= 208 && (fv == 3 || fv == 0)) {    // 13 key tiles, 53 248 B: three workgroups per CU
-    constexpr int smem13 = 2 * 13 * 16 * 128;
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd13_kernel<false>, smem13));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd13_kernel<false><<<B * H, 256, smem13, s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, H, sl);
-  } else if (N <= 224 && fv == 2) {          // query-tile pairs per wave: half the LDS fragment traffic per FLOP
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd2_kernel<14>, fwd_smem(14)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd2_kernel<14><<<B * H, 256, fwd_smem(14), s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, H, sl);
-  } else if (N <= 224) {
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd_kernel<14>, fwd_smem(14)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd_kernel<14><<<B * H, 256, fwd_smem(14), s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, H, sl);
-  } else if (N <= 288) {                   // 257 tokens at 256^2: 18 key tiles = 73.7 KB of K/V, still two workgroups per CU
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd_kernel<18>, fwd_smem(18)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd_kernel<18><<<B * H, 256, fwd_smem(18), s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, H, sl);
-  } else {
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd_kernel<20>, fwd_smem(20)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd_kernel<20><<<B * H, 256, fwd_smem(20), s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, H, sl);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const bf16_t* in = (const bf16_t*)qkv;
+  bf16_t* o = (bf16_t*)out;
+  if (N <= 208 && (fv == 3 || fv == 0))      // 13 key tiles, 53 248 B: three workgroups per CU
+    return mv_launch<attn_fwd13_kernel<false>>(MV_HERE, B * H, 256, fwd13_smem, s, in, o, lse, N, H, sl);
+  if (N <= 224 && fv == 2)                   // query-tile pairs per wave: half the LDS fragment traffic per FLOP
+    return mv_launch<attn_fwd2_kernel<14>>(MV_HERE, B * H, 256, fwd_smem(14), s, in, o, lse, N, H, sl);
+  if (N <= 224) return mv_launch<attn_fwd_kernel<14>>(MV_HERE, B * H, 256, fwd_smem(14), s, in, o, lse, N, H, sl);
+  if (N <= 288)                              // 257 tokens at 256^2: 18 key tiles = 73.7 KB of K/V, still two workgroups per CU
+    return mv_launch<attn_fwd_kernel<18>>(MV_HERE, B * H, 256, fwd_smem(18), s, in, o, lse, N, H, sl);
+  return mv_launch<attn_fwd_kernel<20>>(MV_HERE, B * H, 256, fwd_smem(20), s, in, o, lse, N, H, sl);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1622,18 +1600,11 @@ extern "C" int mv_attention_fwd_f16(const void* qkv16, float* out, float* lse, i
   MV_REQUIRE(N <= 288, MV_ERR_UNSUPPORTED);
   MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(out), MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
-  if (N <= 208) {
-    constexpr int smem13 = 2 * 13 * 16 * 128;
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd13_kernel<true>, smem13));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd13_kernel<true><<<B * H, 256, smem13, (hipStream_t)stream>>>((const bf16_t*)qkv16, (bf16_t*)out, lse, N, H, scale * LOG2E);
-  } else {                                   // the 257-token case (256^2 inputs): 18 key tiles, two workgroups per CU
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_fwd_kernel<18, true>, fwd_smem(18)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_fwd_kernel<18, true><<<B * H, 256, fwd_smem(18), (hipStream_t)stream>>>((const bf16_t*)qkv16, (bf16_t*)out, lse, N, H, scale * LOG2E);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bf16_t* in = (const bf16_t*)qkv16;
+  if (N <= 208) return mv_launch<attn_fwd13_kernel<true>>(MV_HERE, B * H, 256, fwd13_smem, s, in, (bf16_t*)out, lse, N, H, scale * LOG2E);
+  // the 257-token case (256^2 inputs): 18 key tiles, two workgroups per CU
+  return mv_launch<attn_fwd_kernel<18, true>>(MV_HERE, B * H, 256, fwd_smem(18), s, in, (bf16_t*)out, lse, N, H, scale * LOG2E);
 }
 
 extern "C" int mv_attention_bwd_prep_f16(const float* dout, const float* out, void* dout16, float* delta, float* gscale,
@@ -1646,6 +1617,20 @@ extern "C" int mv_attention_bwd_prep_f16(const float* dout, const float* out, vo
   return MV_OK;
 }
 
+namespace {
+template <int SPLIT>
+int launch_bwd_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse, const float* gscale, void* dqkv,
+                   float* colsum, int B, int N, int H, float scale, hipStream_t s) {
+  const bf16_t *in = (const bf16_t*)qkv16, *dout = (const bf16_t*)dout16, *none = nullptr;
+  if (N <= 208)
+    return mv_launch<attn_bwd4_kernel<4, true, SPLIT>>(MV_HERE, B * H, 256, bwd4_smem, s, in, none, dout, lse, (bf16_t*)dqkv, colsum,
+                                                       N, H, scale, delta, gscale);
+  // 209 .. 288 tokens: the two-pass kernel (the 257-token case)
+  return mv_launch<attn_bwd2p_kernel<9, true, SPLIT>>(MV_HERE, B * H, 256, bwd2p_smem(9), s, in, none, dout, lse, (bf16_t*)dqkv,
+                                                      colsum, N, H, scale, delta, gscale);
+}
+}  // namespace
+
 extern "C" int mv_attention_bwd_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse,
                                     const float* gscale, void* dqkv, int nseg, float* colsum, int B, int N, int H, float scale,
                                     mv_stream_t stream) {
@@ -1653,32 +1638,10 @@ extern "C" int mv_attention_bwd_f16(const void* qkv16, const void* dout16, const
   MV_REQUIRE(N <= 288 && (nseg == 0 || nseg == 3 || nseg == 6), MV_ERR_UNSUPPORTED);
   MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(dout16) && mv_aligned16(dqkv) && delta && lse && gscale, MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
-  constexpr int smem4 = 224 * 128 + 208 * 128 + 8192 + 224 * 64 + 2 * 224 * 4;
   hipStream_t s = (hipStream_t)stream;
-#define MV_BWD_F16(SPLIT_)                                                                                                   \
-  {                                                                                                                          \
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd4_kernel<4, true, SPLIT_>, smem4));                                    \
-    if (a) return MV_ERR_LAUNCH;                                                                                             \
-    attn_bwd4_kernel<4, true, SPLIT_><<<B * H, 256, smem4, s>>>((const bf16_t*)qkv16, nullptr, (const bf16_t*)dout16, lse,   \
-                                                                (bf16_t*)dqkv, colsum, N, H, scale, delta, gscale);           \
-  }
-#define MV_BWD2P_F16(SPLIT_)                                                                                                  \
-  {                                                                                                                          \
-    constexpr int smem2 = 2 * 288 * 128 + 2 * 288 * 4 + 4 * 192 * 4;                                                         \
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd2p_kernel<9, true, SPLIT_>, smem2));                                   \
-    if (a) return MV_ERR_LAUNCH;                                                                                             \
-    attn_bwd2p_kernel<9, true, SPLIT_><<<B * H, 256, smem2, s>>>((const bf16_t*)qkv16, nullptr, (const bf16_t*)dout16, lse,  \
-                                                                 (bf16_t*)dqkv, colsum, N, H, scale, delta, gscale);          \
-  }
-  if (N <= 208) {
-    if (nseg == 0) MV_BWD_F16(0) else if (nseg == 3) MV_BWD_F16(3) else MV_BWD_F16(6)
-  } else {                                   // 209 .. 288 tokens: the two-pass kernel (the 257-token case)
-    if (nseg == 0) MV_BWD2P_F16(0) else if (nseg == 3) MV_BWD2P_F16(3) else MV_BWD2P_F16(6)
-  }
-#undef MV_BWD2P_F16
-#undef MV_BWD_F16
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return nseg == 0   ? launch_bwd_f16<0>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s)
+         : nseg == 3 ? launch_bwd_f16<3>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s)
+                     : launch_bwd_f16<6>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s);
 }
 
 extern "C" int mv_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
@@ -1692,41 +1655,18 @@ extern "C" int mv_attention_bwd(const void* qkv, const void* out, const void* do
   const int forced = g_bwd_variant.load(std::memory_order_relaxed);
   const bool force8 = forced == 8;
   const bool two_pass = forced == 2 || (forced == 0 && N > 208);
+  const bf16_t *in = (const bf16_t*)qkv, *o = (const bf16_t*)out, *d = (const bf16_t*)dout;
+  bf16_t* dq = (bf16_t*)dqkv;
+  const float* nof = nullptr;                     // delta_in, gscale: the half kernels' inputs
   if (N <= 288 && !force8 && two_pass) {
-    if (N <= 224) {
-      constexpr int smem = 2 * 224 * 128 + 2 * 224 * 4 + 4 * 192 * 4;
-      const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd2p_kernel<7>, smem));
-      if (a) return MV_ERR_LAUNCH;
-      attn_bwd2p_kernel<7><<<B * H, 256, smem, s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                                                   (bf16_t*)dqkv, colsum, N, H, scale);
-    } else {
-      constexpr int smem = 2 * 288 * 128 + 2 * 288 * 4 + 4 * 192 * 4;
-      const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd2p_kernel<9>, smem));
-      if (a) return MV_ERR_LAUNCH;
-      attn_bwd2p_kernel<9><<<B * H, 256, smem, s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                                                   (bf16_t*)dqkv, colsum, N, H, scale);
-    }
-  } else if (N <= 208 && !force8) {
-    constexpr int smem4 = 224 * 128 + 208 * 128 + 8192 + 224 * 64 + 2 * 224 * 4;   // 79,616 B: two workgroups per CU
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd4_kernel<4>, smem4) | set_smem(attn_bwd4_kernel<2>, smem4));
-    if (a) return MV_ERR_LAUNCH;
-    if (forced == 5 && N > 192)                   // two waves of 512 registers per workgroup (7 + 6 key tiles)
-      attn_bwd4_kernel<2><<<B * H, 128, smem4, s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                                                   (bf16_t*)dqkv, colsum, N, H, scale);
-    else
-      attn_bwd4_kernel<4><<<B * H, 256, smem4, s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                                                   (bf16_t*)dqkv, colsum, N, H, scale);
-  } else if (N <= 224) {
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd_kernel<14, 2>, bwd_smem(14)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_bwd_kernel<14, 2><<<B * H, 512, bwd_smem(14), s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
-                                                          lse, (bf16_t*)dqkv, colsum, N, H, scale);
-  } else {
-    const int a = MV_ONCE_PER_DEVICE(set_smem(attn_bwd_kernel<20, 3>, bwd_smem(20)));
-    if (a) return MV_ERR_LAUNCH;
-    attn_bwd_kernel<20, 3><<<B * H, 512, bwd_smem(20), s>>>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
-                                                          lse, (bf16_t*)dqkv, colsum, N, H, scale);
+    if (N <= 224) return mv_launch<attn_bwd2p_kernel<7>>(MV_HERE, B * H, 256, bwd2p_smem(7), s, in, o, d, lse, dq, colsum, N, H, scale, nof, nof);
+    return mv_launch<attn_bwd2p_kernel<9>>(MV_HERE, B * H, 256, bwd2p_smem(9), s, in, o, d, lse, dq, colsum, N, H, scale, nof, nof);
   }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  if (N <= 208 && !force8) {                      // 79,616 B: two workgroups per CU
+    if (forced == 5 && N > 192)                   // two waves of 512 registers per workgroup (7 + 6 key tiles)
+      return mv_launch<attn_bwd4_kernel<2>>(MV_HERE, B * H, 128, bwd4_smem, s, in, o, d, lse, dq, colsum, N, H, scale, nof, nof);
+    return mv_launch<attn_bwd4_kernel<4>>(MV_HERE, B * H, 256, bwd4_smem, s, in, o, d, lse, dq, colsum, N, H, scale, nof, nof);
+  }
+  if (N <= 224) return mv_launch<attn_bwd_kernel<14, 2>>(MV_HERE, B * H, 512, bwd_smem(14), s, in, o, d, lse, dq, colsum, N, H, scale);
+  return mv_launch<attn_bwd_kernel<20, 3>>(MV_HERE, B * H, 512, bwd_smem(20), s, in, o, d, lse, dq, colsum, N, H, scale);
 }

@@ -435,27 +435,17 @@ template <int NT>
 int launch_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int N,
                         int H, float scale, hipStream_t s) {
   constexpr size_t lds = ((size_t)2 * NT * 16 * AF_DH + 2 * NT * 16) * sizeof(float);
-  const int attr = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_f32_kernel<NT>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -1);
-  if (attr) return MV_ERR_LAUNCH;
-  attn_bwd_f32_kernel<NT><<<B * H, 512, lds, s>>>(qkv, out, dout, lse, dqkv, N, H, scale);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<attn_bwd_f32_kernel<NT>>(MV_HERE, B * H, 512, lds, s, qkv, out, dout, lse, dqkv, N, H, scale);
 }
 
 template <int NT, bool Q8>
 int launch_attn_f32(const float* qkv, void* out, int B, int N, int H, float scale, float q_inv, float q_zp, hipStream_t s,
                     float* lse = nullptr) {
   constexpr size_t lds = (size_t)2 * NT * 16 * AF_DH * sizeof(float);
-  const int attr = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_f32_kernel<NT, Q8>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -1);
-  if (attr) return MV_ERR_LAUNCH;
   const int n_cu = mv_cu_count();                         // of the current device (one cached value per device)
   const int items = B * H;
-  attn_fwd_f32_kernel<NT, Q8><<<items < n_cu ? items : n_cu, 512, lds, s>>>(qkv, (float*)out, N, H, scale, q_inv, q_zp, lse,
-                                                                             items);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<attn_fwd_f32_kernel<NT, Q8>>(MV_HERE, items < n_cu ? items : n_cu, 512, lds, s, qkv, (float*)out, N, H, scale,
+                                                q_inv, q_zp, lse, items);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -882,22 +872,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_long_f32_kernel(const float* 
   }
 }
 
-template <typename K>
-int lf_set_smem(K kernel, int bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess
-             ? 0 : -1;
-}
-
 template <int OUT>
 int launch_attn_fwd_long_f32(const float* qkv, void* out, float* lse, int B, int N, int H, float scale, float q_inv,
                              float q_zp, hipStream_t s) {
   constexpr int lds = 2 * LF_STAGE * (int)sizeof(float);
-  if (MV_ONCE_PER_DEVICE(lf_set_smem(attn_fwd_long_f32_kernel<OUT>, lds))) return MV_ERR_LAUNCH;
   const long nqb = (N + LF_ROWS - 1) / LF_ROWS;
-  attn_fwd_long_f32_kernel<OUT><<<(unsigned)(nqb * B * H), 512, lds, s>>>(qkv, out, lse, N, H, (int)nqb, scale * AF_LOG2E,
-                                                                           q_inv, q_zp);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<attn_fwd_long_f32_kernel<OUT>>(MV_HERE, (unsigned)(nqb * B * H), 512, lds, s, qkv, out, lse, N, H, (int)nqb,
+                                                  scale * AF_LOG2E, q_inv, q_zp);
 }
 
 }  // namespace
@@ -982,11 +963,9 @@ extern "C" int mv_attention_bwd_long_f32(const float* qkv, const float* out, con
   if (B == 0) return MV_OK;
   hipStream_t s = (hipStream_t)stream;
   constexpr int lds_dkdv = (2 * LF_STAGE + 4 * LF_BLK) * (int)sizeof(float), lds_dq = 2 * LF_STAGE * (int)sizeof(float);
-  if (MV_ONCE_PER_DEVICE(lf_set_smem(attn_bwd_dkdv_long_f32_kernel, lds_dkdv) | lf_set_smem(attn_bwd_dq_long_f32_kernel, lds_dq)))
-    return MV_ERR_LAUNCH;
+  const unsigned grid = (unsigned)(nb * B * H);
   attn_delta_long_f32_kernel<<<(unsigned)((rows * 16 + 255) / 256), 256, 0, s>>>(out, dout, delta_ws, rows, N, H);
-  attn_bwd_dkdv_long_f32_kernel<<<(unsigned)(nb * B * H), 512, lds_dkdv, s>>>(qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
-  attn_bwd_dq_long_f32_kernel<<<(unsigned)(nb * B * H), 512, lds_dq, s>>>(qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const int rc = mv_launch<attn_bwd_dkdv_long_f32_kernel>(MV_HERE, grid, 512, lds_dkdv, s, qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
+  if (rc != MV_OK) return rc;
+  return mv_launch<attn_bwd_dq_long_f32_kernel>(MV_HERE, grid, 512, lds_dq, s, qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
 }

@@ -5,6 +5,7 @@
 // although it wins per shape in isolation on the K = 768 products (+3 % on qkv in round 4).  Kept here as source for the record;
 // it was written against the helpers of gemm_bf16.hip at commit 'round 4 persistent port' and is meant to be #included into that
 // file after gemm_nt_8phase_kernel (namespace-local), with the dispatch arm at the end of this file inside launch_nt.
+// Its dispatch arm still uses MV_ONCE_PER_DEVICE, which mv_common.h no longer has: a revival launches through mv_launch instead.
 
 // ------------------------------------------------------------------------------------------------
 // NT 8-phase kernel, PERSISTENT: one workgroup per CU walks whole interior tiles; stores drain under the next tile

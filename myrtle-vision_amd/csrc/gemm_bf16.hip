@@ -1784,14 +1784,6 @@ bool tn_use_ring(int M, int N, int Kc) {
   return pl.tiles_m * pl.tiles_n * pl.splits >= 160;
 }
 
-template <typename K>
-int set_smem(K kernel) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             SMEM_BYTES) == hipSuccess
-             ? 0
-             : -1;
-}
-
 // Tail split of the 8-phase kernel: tiles beyond the last full round of the 256 CUs become two HALF items each when
 // that round would be less than half full (otherwise a whole-tile round is already the better use of the chip).
 constexpr int NT_CUS = 256;
@@ -1810,19 +1802,58 @@ constexpr int NT_FEATURES_DEFAULT = 2;
 // Column-band width (in 256-column tiles) for a product with tiles_n tile columns and contraction K, or 0.  MV_NT_BAND=W forces W
 // wherever it divides tiles_n (shape scans).  Measured per shape (round 3, finding 37; round 4): only the qkv projection
 // (9 tile columns, K = 768) gains; N = 3072 loses with every width.
-inline int nt_band_width(int tiles_n, int K, bool whole_tiles_only) {
+inline int nt_band_width(int tiles_n, int K) {
   static const int forced = getenv("MV_NT_BAND") ? atoi(getenv("MV_NT_BAND")) : 0;
   if (forced > 0) return tiles_n % forced == 0 && tiles_n > forced ? forced : 0;
-  (void)whole_tiles_only;
   return (tiles_n == 9 && K <= 1024) ? 3 : 0;
+}
+
+// The forced NT variant (MV_GEMM_TILE, mv_gemm_force_variant) decoded: which kernel family, which optional features of the 8-phase
+// kernel, and how its tail tiles are cut.  The integer values are what tests and tools pass; no code outside this table names them.
+enum NtFamily { NT_FAMILY_AUTO, NT_FAMILY_128, NT_FAMILY_RING, NT_FAMILY_P8 };   // P8 / RING: wherever that kernel is legal, else the 128-tile kernels
+enum NtTail { NT_TAIL_AUTO, NT_TAIL_WHOLE, NT_TAIL_HALVES };                     // nt_full_tiles | whole tiles only | half items only (A/B)
+constexpr int NT_FEATURE_BANDS = 2;
+struct NtForce {
+  int value;
+  NtFamily family;
+  int features;
+  NtTail tail;
+};
+constexpr NtForce NT_FORCE[] = {
+    {0, NT_FAMILY_AUTO, NT_FEATURES_DEFAULT, NT_TAIL_AUTO},
+    {128, NT_FAMILY_128, NT_FEATURES_DEFAULT, NT_TAIL_AUTO},
+    {2564, NT_FAMILY_RING, NT_FEATURES_DEFAULT, NT_TAIL_AUTO},
+    {2568, NT_FAMILY_P8, NT_FEATURES_DEFAULT, NT_TAIL_AUTO},
+    {25680, NT_FAMILY_P8, NT_FEATURES_DEFAULT, NT_TAIL_WHOLE},
+    {25681, NT_FAMILY_P8, NT_FEATURES_DEFAULT, NT_TAIL_HALVES},
+    // 3000 / 3002: automatic dispatch with the column bands of the 8-phase kernel off / on (A/B in one process, tools/ab_step.py);
+    // 3100 / 3102: the same with the 8-phase kernel forced wherever it is legal, as 2568 (unit tests on small shapes)
+    {3000, NT_FAMILY_AUTO, 0, NT_TAIL_AUTO},
+    {3002, NT_FAMILY_AUTO, NT_FEATURE_BANDS, NT_TAIL_AUTO},
+    {3100, NT_FAMILY_P8, 0, NT_TAIL_AUTO},
+    {3102, NT_FAMILY_P8, NT_FEATURE_BANDS, NT_TAIL_AUTO},
+};
+inline const NtForce* nt_force_find(int value) {
+  for (const NtForce& f : NT_FORCE)
+    if (f.value == value) return &f;
+  return nullptr;
+}
+
+// One launch of the 8-phase kernel over the 256x256 tiles of an [M, N] output, `splits` work items per tile (KSPLIT): the whole
+// and the half items, the grid, the LDS.  lda, ldb and K are in the 2-byte elements the kernel is written in.
+template <int EPI, typename CT, int OPK = NT_BF16, bool KSPLIT = false>
+int launch_p8(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, EpiArgs ep, hipStream_t s,
+              int splits = 1, NtTail tail = NT_TAIL_AUTO, bool bands = false) {
+  const int t2n = mv_cdiv(N, BN2), items = mv_cdiv(M, BM2) * t2n * splits;
+  const int full = tail == NT_TAIL_WHOLE ? items : tail == NT_TAIL_HALVES ? 0 : nt_full_tiles(items);
+  if (bands) ep.band = nt_band_width(t2n, K);
+  return mv_launch<gemm_nt_8phase_kernel<EPI, CT, OPK, KSPLIT>>(MV_HERE, full + 2 * (items - full), 512, P8_SMEM, s, (const bf16_t*)A,
+                                                                lda, (const bf16_t*)B, ldb, (CT*)C, ldc, M, N, K, t2n, ep, full, 0);
 }
 
 template <int EPI, typename CT>
 int launch_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, EpiArgs ep,
               hipStream_t s) {
-  const int attr = MV_ONCE_PER_DEVICE(set_smem(gemm_nt_kernel<EPI, CT>) | set_smem(gemm_nt_glds_kernel<EPI, CT>) |
-                          set_smem(gemm_nt_glds_kernel<EPI, CT, false>));
-  if (attr != 0) return MV_ERR_LAUNCH;
   const int tiles_m = mv_cdiv(M, BM), tiles_n = mv_cdiv(N, BN);
   const int t2m = mv_cdiv(M, BM2), t2n = mv_cdiv(N, BN2);
   // Kernel choice (measured on MI355X, tools/bench_gemm.py, M = 50432): the 256x256 ring kernel wins whenever its
@@ -1830,17 +1861,8 @@ int launch_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, 
   // otherwise two 128x128 workgroups per CU overlap each other's epilogues better.  Where the ring kernel would be
   // picked and K % 128 == 0, the 8-phase kernel replaces it (+6-14 % on every ViT-B shape: whole 128-byte lines per
   // DMA row, 16-MFMA phases).  MV_GEMM_TILE = 128 | 2564 (ring) | 2568 (8-phase) forces a variant (tuning, tests).
-  int force = g_force_nt.load(std::memory_order_relaxed);
-  // 3000 / 3002: automatic dispatch with the column bands of the 8-phase kernel off / on (A/B in one process, tools/ab_step.py);
-  // 3100 / 3102: the same with the 8-phase kernel forced wherever it is legal, as 2568 (unit tests on small shapes)
-  int feat = NT_FEATURES_DEFAULT;
-  if (force == 3000 || force == 3002) {
-    feat = force - 3000;
-    force = 0;
-  } else if (force == 3100 || force == 3102) {
-    feat = force - 3100;
-    force = 2568;
-  }
+  const NtForce* const known = nt_force_find(g_force_nt.load(std::memory_order_relaxed));
+  const NtForce force = known ? *known : NT_FORCE[1];       // an MV_GEMM_TILE outside the table picks no 256-tile kernel: as 128
   const bool ring_ok = K > 0 && K % BKR == 0;
   const bool ring_pick = ring_ok && ((long)t2m * t2n >= 1024 || (K >= 2048 && (long)t2m * t2n >= 256));
   const bool p8_ok = K >= 128 && K % 128 == 0 && (long)M * lda < (1L << 31) && (long)N * ldb < (1L << 31);
@@ -1853,38 +1875,22 @@ int launch_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, 
   const long t2 = (long)t2m * t2n;
   const bool p8_halves = p8_ok && !ring_pick && t2 >= NT_CUS / 4 && t2 < NT_CUS / 2;
   const bool p8_pick = p8_ok && (ring_pick || t2 >= NT_CUS / 4);
-  if (((force == 2568 || force == 25680 || force == 25681) && p8_ok) || (force == 0 && p8_pick)) {
-    const int a8 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_8phase_kernel<EPI, CT>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, P8_SMEM) == hipSuccess ? 0 : -1);
-    if (a8) return MV_ERR_LAUNCH;
-    // 25680: whole tiles only, 25681: half items only (A/B)
-    const int tiles = t2m * t2n,
-              full = force == 25680 ? tiles : (force == 25681 || (force == 0 && p8_halves)) ? 0 : nt_full_tiles(tiles);
-    if (feat & 2) ep.band = nt_band_width(t2n, K, full == tiles);
-    gemm_nt_8phase_kernel<EPI, CT><<<full + 2 * (tiles - full), 512, P8_SMEM, s>>>(
-        (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (CT*)C, ldc, M, N, K, t2n, ep, full, 0);
-    MV_CHECK_LAUNCH();
-    return MV_OK;
+  if ((force.family == NT_FAMILY_P8 && p8_ok) || (force.family == NT_FAMILY_AUTO && p8_pick)) {
+    const NtTail tail = (force.family == NT_FAMILY_AUTO && p8_halves) ? NT_TAIL_HALVES : force.tail;
+    return launch_p8<EPI, CT>(A, lda, B, ldb, C, ldc, M, N, K, ep, s, 1, tail, (force.features & NT_FEATURE_BANDS) != 0);
   }
-  if ((force == 2564 && ring_ok) || (force == 0 && ring_pick)) {
-    const int a4 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_ring_kernel<EPI, CT, 4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 4 * RSTAGE_BYTES) == hipSuccess ? 0 : -1);
-    if (a4) return MV_ERR_LAUNCH;
-    gemm_nt_ring_kernel<EPI, CT, 4><<<t2m * t2n, 512, 4 * RSTAGE_BYTES, s>>>((const bf16_t*)A, lda, (const bf16_t*)B, ldb,
-                                                                              (CT*)C, ldc, M, N, K, t2n, ep);
-  } else if (K > 0 && K % BK == 0) {
+  const bf16_t *a = (const bf16_t*)A, *b = (const bf16_t*)B;
+  if ((force.family == NT_FAMILY_RING && ring_ok) || (force.family == NT_FAMILY_AUTO && ring_pick))
+    return mv_launch<gemm_nt_ring_kernel<EPI, CT, 4>>(MV_HERE, t2m * t2n, 512, 4 * RSTAGE_BYTES, s, a, lda, b, ldb, (CT*)C, ldc, M, N, K,
+                                                      t2n, ep);
+  const int tiles = tiles_m * tiles_n;
+  if (K > 0 && K % BK == 0) {
     if ((long)M * lda < (1L << 31) && (long)N * ldb < (1L << 31))       // 32-bit byte offsets of the buffer-descriptor DMA
-      gemm_nt_glds_kernel<EPI, CT><<<tiles_m * tiles_n, 256, SMEM_BYTES, s>>>((const bf16_t*)A, lda, (const bf16_t*)B, ldb,
-                                                                               (CT*)C, ldc, M, N, K, tiles_n, ep);
-    else
-      gemm_nt_glds_kernel<EPI, CT, false><<<tiles_m * tiles_n, 256, SMEM_BYTES, s>>>((const bf16_t*)A, lda, (const bf16_t*)B, ldb,
-                                                                                      (CT*)C, ldc, M, N, K, tiles_n, ep);
+      return mv_launch<gemm_nt_glds_kernel<EPI, CT>>(MV_HERE, tiles, 256, SMEM_BYTES, s, a, lda, b, ldb, (CT*)C, ldc, M, N, K, tiles_n, ep);
+    return mv_launch<gemm_nt_glds_kernel<EPI, CT, false>>(MV_HERE, tiles, 256, SMEM_BYTES, s, a, lda, b, ldb, (CT*)C, ldc, M, N, K, tiles_n,
+                                                          ep);
   }
-  else
-    gemm_nt_kernel<EPI, CT><<<tiles_m * tiles_n, 256, SMEM_BYTES, s>>>((const bf16_t*)A, lda, (const bf16_t*)B, ldb,
-                                                                        (CT*)C, ldc, M, N, K, tiles_n, ep);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<gemm_nt_kernel<EPI, CT>>(MV_HERE, tiles, 256, SMEM_BYTES, s, a, lda, b, ldb, (CT*)C, ldc, M, N, K, tiles_n, ep);
 }
 
 }  // namespace
@@ -1968,16 +1974,8 @@ extern "C" int mv_gemm_nt_bf16_ksplit(const void* A, int lda, const void* B, int
   MV_REQUIRE(mv_aligned16(A) && mv_aligned16(B) && mv_aligned16(slabs), MV_ERR_ALIGN);
   // buffer-descriptor DMA: BYTE offsets and the descriptor's extent are 32-bit (as in p8_ok / launch_nt)
   MV_REQUIRE((long)M * lda < (1L << 31) && (long)N * ldb < (1L << 31), MV_ERR_UNSUPPORTED);
-  const int a8 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_8phase_kernel<MV_EPI_NONE, float, NT_BF16, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, P8_SMEM) == hipSuccess ? 0 : -1);
-  if (a8) return MV_ERR_LAUNCH;
-  const int t2m = mv_cdiv(M, BM2), t2n = mv_cdiv(N, BN2);
-  const int tiles = t2m * t2n, items = tiles * splits, full = nt_full_tiles(items);
-  EpiArgs ep{1.0f, bias, nullptr, 0, 0, nullptr, 0, nullptr, 0.f, 0.f, tiles, K / splits, (long)M * N};
-  gemm_nt_8phase_kernel<MV_EPI_NONE, float, NT_BF16, true><<<full + 2 * (items - full), 512, P8_SMEM, (hipStream_t)stream>>>(
-      (const bf16_t*)A, lda, (const bf16_t*)B, ldb, slabs, N, M, N, K / splits, t2n, ep, full, 0);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  EpiArgs ep{1.0f, bias, nullptr, 0, 0, nullptr, 0, nullptr, 0.f, 0.f, mv_cdiv(M, BM2) * mv_cdiv(N, BN2), K / splits, (long)M * N};
+  return launch_p8<MV_EPI_NONE, float, NT_BF16, true>(A, lda, B, ldb, slabs, N, M, N, K / splits, ep, (hipStream_t)stream, splits);
 }
 
 // dW of an fp32 nn.Linear as a bf16x6 product (see mv_split3_bf16): A6 = split3(dY) [rows, 6 M], B6 = split3(X) [rows, 6 N],
@@ -1986,6 +1984,21 @@ extern "C" int mv_gemm_nt_bf16_ksplit(const void* A, int lda, const void* B, int
 // kernel walks 6 * rows contraction rows through the segment table -- the SAME splits the dX and forward products use, no
 // stacked copies.
 namespace {
+// The frame every split-K TN product shares.  One split that adds to nothing writes C itself; otherwise the splits write [M][N]
+// slabs of the workspace and splitk_reduce_kernel sums them into C.  launch(out, ld_out, slab_stride) starts the main kernel.
+template <typename Launch>
+int tn_splitk(const TnPlan& pl, float* C, int ldc, int M, int N, int accumulate, float* workspace, hipStream_t s, Launch launch) {
+  const bool direct = pl.splits == 1 && !accumulate;
+  const long slab_stride = (long)M * N;
+  const int rc = launch(direct ? C : workspace, direct ? (long)ldc : (long)N, direct ? 0 : slab_stride);
+  if (rc != MV_OK || direct) return rc;
+  int grid = mv_cdiv(slab_stride, 256);
+  if (grid > 2048) grid = 2048;
+  splitk_reduce_kernel<<<grid, 256, 0, s>>>(workspace, slab_stride, pl.splits, C, ldc, M, N, accumulate);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
 // NSEG = 6: the bf16x6 pairings over three pieces per operand; NSEG = 3: the bf16x3 pairings (0,0) (0,1) (1,0) over TWO pieces per
 // operand in the [p0 p0 p1] layout of mv_split2_bf16 (p0 at column block 0, p1 at block 2).
 template <int NSEG>
@@ -1999,11 +2012,6 @@ int launch_tn_segments(const void* A, const void* B, float* C, int ldc, int M, i
   MV_REQUIRE(workspace_bytes >= mv_gemm_tn_workspace_bytes(M, N, Kc), MV_ERR_WORKSPACE);
   const TnPlan pl = tn_plan256(M, N, Kc);
   const int tiles_mn = pl.tiles_m * pl.tiles_n;
-  const bool direct = pl.splits == 1;
-  const long slab_stride = (long)M * N;
-  const int a4 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_ring_kernel<4, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * RSTAGE_BYTES) == hipSuccess ? 0 : -1);
-  if (a4) return MV_ERR_LAUNCH;
   TnSeg seg;
   seg.tiles = rows / BKR;
   const int pa[6] = {0, 0, 1, 0, 1, 2}, pb[6] = {0, 1, 0, 2, 1, 0}, block[3] = {0, 2, 5};
@@ -2012,17 +2020,11 @@ int launch_tn_segments(const void* A, const void* B, float* C, int ldc, int M, i
     seg.a[i] = block[pa[j]] * M;
     seg.b[i] = block[pb[j]] * N;
   }
-  gemm_tn_ring_kernel<4, true><<<tiles_mn * pl.splits, 512, 4 * RSTAGE_BYTES, s>>>(
-      (const bf16_t*)A, NSEG * M, (const bf16_t*)B, NSEG * N, direct ? C : workspace, direct ? (long)ldc : (long)N,
-      direct ? 0 : slab_stride, M, N, Kc, pl.tiles_n, tiles_mn, pl.steps_per_split, seg);
-  MV_CHECK_LAUNCH();
-  if (!direct) {
-    int grid = mv_cdiv(slab_stride, 256);
-    if (grid > 2048) grid = 2048;
-    splitk_reduce_kernel<<<grid, 256, 0, s>>>(workspace, slab_stride, pl.splits, C, ldc, M, N, 0);
-    MV_CHECK_LAUNCH();
-  }
-  return MV_OK;
+  return tn_splitk(pl, C, ldc, M, N, 0, workspace, s, [&](float* out, long ld_out, long slab_stride) {
+    return mv_launch<gemm_tn_ring_kernel<4, true>>(MV_HERE, tiles_mn * pl.splits, 512, 4 * RSTAGE_BYTES, s, (const bf16_t*)A, NSEG * M,
+                                                   (const bf16_t*)B, NSEG * N, out, ld_out, slab_stride, M, N, Kc, pl.tiles_n, tiles_mn,
+                                                   pl.steps_per_split, seg);
+  });
 }
 }  // namespace
 
@@ -2042,32 +2044,8 @@ namespace {
 template <int EPI, typename CT>
 int launch_nt_i8(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, EpiArgs ep,
                  hipStream_t s) {
-  const int a8 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_8phase_kernel<EPI, CT, NT_I8>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, P8_SMEM) == hipSuccess ? 0 : -1);
-  if (a8) return MV_ERR_LAUNCH;
-  const int t2m = mv_cdiv(M, BM2), t2n = mv_cdiv(N, BN2);
-  const int tiles = t2m * t2n, full = nt_full_tiles(tiles);
   // bytes -> the bf16-element geometry the kernel is written in
-  gemm_nt_8phase_kernel<EPI, CT, NT_I8><<<full + 2 * (tiles - full), 512, P8_SMEM, s>>>(
-      (const bf16_t*)A, lda / 2, (const bf16_t*)B, ldb / 2, (CT*)C, ldc, M, N, K / 2, t2n, ep, full, 0);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
-}
-}  // namespace
-
-namespace {
-template <int EPI, typename CT>
-int launch_nt_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, EpiArgs ep,
-                  hipStream_t s) {
-  const int a8 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_8phase_kernel<EPI, CT, NT_F16>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, P8_SMEM) == hipSuccess ? 0 : -1);
-  if (a8) return MV_ERR_LAUNCH;
-  const int t2m = mv_cdiv(M, BM2), t2n = mv_cdiv(N, BN2);
-  const int tiles = t2m * t2n, full = nt_full_tiles(tiles);
-  gemm_nt_8phase_kernel<EPI, CT, NT_F16><<<full + 2 * (tiles - full), 512, P8_SMEM, s>>>(
-      (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (CT*)C, ldc, M, N, K, t2n, ep, full, 0);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return launch_p8<EPI, CT, NT_I8>(A, lda / 2, B, ldb / 2, C, ldc, M, N, K / 2, ep, s);
 }
 }  // namespace
 
@@ -2083,10 +2061,10 @@ extern "C" int mv_gemm_nt_f16(const void* A, int lda, const void* B, int ldb, vo
   hipStream_t s = (hipStream_t)stream;
   EpiArgs ep{1.0f, bias, aux, ld_aux, 0, out2, ld_out2, nullptr, 0.f, 0.f};
   switch (epilogue) {
-    case MV_EPI_NONE: return launch_nt_f16<MV_EPI_NONE, float>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
+    case MV_EPI_NONE: return launch_p8<MV_EPI_NONE, float, NT_F16>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
     case MV_EPI_RESIDUAL:
       MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-      return launch_nt_f16<MV_EPI_RESIDUAL, float>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
+      return launch_p8<MV_EPI_RESIDUAL, float, NT_F16>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
     default: return MV_ERR_UNSUPPORTED;
   }
 }
@@ -2094,17 +2072,9 @@ extern "C" int mv_gemm_nt_f16(const void* A, int lda, const void* B, int ldb, vo
 namespace {
 template <int EPI, typename CT>
 int launch_nt_f8c(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, EpiArgs ep, hipStream_t s) {
-  const int a8 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_8phase_kernel<EPI, CT, NT_F8C>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, P8_SMEM) == hipSuccess ? 0 : -1);
-  if (a8) return MV_ERR_LAUNCH;
-  const int t2m = mv_cdiv(M, BM2), t2n = mv_cdiv(N, BN2);
-  const int tiles = t2m * t2n, full = nt_full_tiles(tiles);
   ep.f8_tiles16 = K / 64;
   // a row of 4 K bytes in the 2-byte geometry the kernel is written in: 2 K "elements", K / 32 K-tiles
-  gemm_nt_8phase_kernel<EPI, CT, NT_F8C><<<full + 2 * (tiles - full), 512, P8_SMEM, s>>>(
-      (const bf16_t*)A, lda / 2, (const bf16_t*)B, ldb / 2, (CT*)C, ldc, M, N, 2 * K, t2n, ep, full, 0);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return launch_p8<EPI, CT, NT_F8C>(A, lda / 2, B, ldb / 2, C, ldc, M, N, 2 * K, ep, s);
 }
 }  // namespace
 
@@ -2161,8 +2131,7 @@ extern "C" int mv_gemm_nt_i8(const void* A, int lda, const void* B, int ldb, voi
 }
 
 extern "C" int mv_gemm_force_variant(int nt_variant, int tn_variant) {
-  const bool nt_ok = nt_variant == 0 || nt_variant == 128 || nt_variant == 2564 || nt_variant == 2568 || nt_variant == 25680 || nt_variant == 25681 ||
-                     nt_variant == 3000 || nt_variant == 3002 || nt_variant == 3100 || nt_variant == 3102;
+  const bool nt_ok = nt_force_find(nt_variant) != nullptr;
   const bool tn_ok = tn_variant == 0 || tn_variant == 128 || tn_variant == 256;
   MV_REQUIRE(nt_ok && tn_ok, MV_ERR_UNSUPPORTED);
   g_force_nt.store(nt_variant, std::memory_order_relaxed);
@@ -2213,8 +2182,6 @@ extern "C" int mv_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, f
   MV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && lda >= ((M + 7) & ~7) && ldb >= ((N + 7) & ~7), MV_ERR_ALIGN);
   MV_REQUIRE(mv_aligned16(A) && mv_aligned16(B) && mv_aligned16(C) && mv_aligned16(workspace), MV_ERR_ALIGN);
   MV_REQUIRE(workspace_bytes >= mv_gemm_tn_workspace_bytes(M, N, Kc), MV_ERR_WORKSPACE);
-  const int attr = MV_ONCE_PER_DEVICE(set_smem(gemm_tn_kernel) | set_smem(gemm_tn_glds_kernel));
-  if (attr != 0) return MV_ERR_LAUNCH;
   hipStream_t s = (hipStream_t)stream;
   // A contraction that is not a whole number of the ring kernel's 32-row stages (197 tokens x a batch that is not a multiple
   // of 32) used to fall to the 128-tile register-staged kernel for ALL of it: the step took as long at batch 48 as at 64.
@@ -2240,37 +2207,23 @@ extern "C" int mv_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, f
   // SLOWER than the ring in the same process, 851 vs 968 and 909 vs 1031 TFLOP/s: the ring's DMA rows are whole
   // 256-byte lines already, so the port only added barriers and halved the bytes in flight.  Not kept.)
   const TnPlan pl = ring ? tn_plan256(M, N, Kc) : tn_plan(M, N, Kc);
-  const int tiles_mn = pl.tiles_m * pl.tiles_n;
-  const bool direct = pl.splits == 1 && !accumulate;
-  const long slab_stride = (long)M * N;
-  if (ring) {
-    const int a4 = MV_ONCE_PER_DEVICE(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_ring_kernel<4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 4 * RSTAGE_BYTES) == hipSuccess ? 0 : -1);
-    if (a4) return MV_ERR_LAUNCH;
-    gemm_tn_ring_kernel<4><<<tiles_mn * pl.splits, 512, 4 * RSTAGE_BYTES, s>>>(
-        (const bf16_t*)A, lda, (const bf16_t*)B, ldb, direct ? C : workspace, direct ? (long)ldc : (long)N,
-        direct ? 0 : slab_stride, M, N, Kc, pl.tiles_n, tiles_mn, pl.steps_per_split, TnSeg{});
-  } else if (Kc > 0 && Kc % BK == 0 && (long)Kc * lda * 2 < (1L << 32) && (long)Kc * ldb * 2 < (1L << 32))
-    gemm_tn_glds_kernel<<<tiles_mn * pl.splits, 256, SMEM_BYTES, s>>>(
-        (const bf16_t*)A, lda, (const bf16_t*)B, ldb, direct ? C : workspace, direct ? (long)ldc : (long)N,
-        direct ? 0 : slab_stride, M, N, Kc, pl.tiles_n, tiles_mn, pl.steps_per_split);
-  else
-    gemm_tn_kernel<<<tiles_mn * pl.splits, 256, SMEM_BYTES, s>>>(
-        (const bf16_t*)A, lda, (const bf16_t*)B, ldb, direct ? C : workspace, direct ? (long)ldc : (long)N,
-        direct ? 0 : slab_stride, M, N, Kc, pl.tiles_n, tiles_mn, pl.steps_per_split);
-  MV_CHECK_LAUNCH();
-  if (!direct) {
-    int grid = mv_cdiv(slab_stride, 256);
-    if (grid > 2048) grid = 2048;
-    splitk_reduce_kernel<<<grid, 256, 0, s>>>(workspace, slab_stride, pl.splits, C, ldc, M, N, accumulate);
-    MV_CHECK_LAUNCH();
-  }
+  const int tiles_mn = pl.tiles_m * pl.tiles_n, grid = tiles_mn * pl.splits;
+  const bf16_t *a = (const bf16_t*)A, *b = (const bf16_t*)B;
+  const int rc = tn_splitk(pl, C, ldc, M, N, accumulate, workspace, s, [&](float* out, long ld_out, long slab_stride) {
+    if (ring)
+      return mv_launch<gemm_tn_ring_kernel<4>>(MV_HERE, grid, 512, 4 * RSTAGE_BYTES, s, a, lda, b, ldb, out, ld_out, slab_stride, M, N, Kc,
+                                               pl.tiles_n, tiles_mn, pl.steps_per_split, TnSeg{});
+    if (Kc > 0 && Kc % BK == 0 && (long)Kc * lda * 2 < (1L << 32) && (long)Kc * ldb * 2 < (1L << 32))
+      return mv_launch<gemm_tn_glds_kernel>(MV_HERE, grid, 256, SMEM_BYTES, s, a, lda, b, ldb, out, ld_out, slab_stride, M, N, Kc, pl.tiles_n,
+                                            tiles_mn, pl.steps_per_split);
+    return mv_launch<gemm_tn_kernel>(MV_HERE, grid, 256, SMEM_BYTES, s, a, lda, b, ldb, out, ld_out, slab_stride, M, N, Kc, pl.tiles_n,
+                                     tiles_mn, pl.steps_per_split);
+  });
+  if (rc != MV_OK) return rc;
   if (colsum) {   // separate pass over dY (next step: produce these sums where dY is written; fusing them here as
                   // ones-operand MFMAs pushed this 235-VGPR kernel into spills)
-    float* cs_ws = workspace + (size_t)pl.splits * (size_t)slab_stride;
-    const int rc = mv_colsum(A, MV_BF16, lda, colsum, accumulate, Kc, M, cs_ws,
-                             (size_t)colsum_parts(Kc) * (size_t)M * sizeof(float), stream);
-    if (rc != MV_OK) return rc;
+    float* cs_ws = workspace + (size_t)pl.splits * (size_t)M * (size_t)N;
+    return mv_colsum(A, MV_BF16, lda, colsum, accumulate, Kc, M, cs_ws, (size_t)colsum_parts(Kc) * (size_t)M * sizeof(float), stream);
   }
   return MV_OK;
 }

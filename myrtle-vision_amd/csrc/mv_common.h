@@ -8,24 +8,9 @@
 #include "../../include/myrtle_vision_hip.h"
 
 #include <atomic>
-// hipFuncSetAttribute acts on the CURRENT device.  The launchers raise a kernel's dynamic-LDS limit once and remember it; the memory is
-// per (call site, device), so a process that drives several GPUs -- not the one-process-per-GPU launch this library is written for, but
-// legal -- does not meet the default 64 KiB limit on its second device.  MV_ONCE_PER_DEVICE(expr): 0 when expr returned 0 on this device
-// (evaluated on first use there), -1 otherwise.
-#define MV_ONCE_PER_DEVICE(expr_)                                                                              \
-  ([&]() -> int {                                                                                              \
-    static std::atomic<signed char> st_[32] = {};                                                              \
-    int d_ = 0;                                                                                                \
-    if (hipGetDevice(&d_) != hipSuccess || d_ < 0 || d_ >= 32) return (expr_) == 0 ? 0 : -1;                   \
-    signed char s_ = st_[d_].load(std::memory_order_acquire);                                                  \
-    if (s_ == 0) {                                                                                             \
-      s_ = (expr_) == 0 ? 1 : -1;                                                                              \
-      st_[d_].store(s_, std::memory_order_release);                                                            \
-    }                                                                                                          \
-    return s_ == 1 ? 0 : -1;                                                                                   \
-  }())
+#include <mutex>
 
-// Compute units of the CURRENT device (persistent-kernel grid sizes), remembered per device like the attributes above.
+// Compute units of the CURRENT device (persistent-kernel grid sizes), remembered per device like the LDS grants of mv_launch below.
 inline int mv_cu_count() {
   static std::atomic<int> n_[32] = {};
   int d = 0;
@@ -74,16 +59,55 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 
 // ---- launch plumbing ------------------------------------------------------------------------
-#define MV_CHECK_LAUNCH()                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = hipGetLastError();                                                            \
-    if (e__ != hipSuccess) {                                                                       \
-      if (getenv("MV_DEBUG"))                                                                      \
-        fprintf(stderr, "[myrtle_vision_hip] %s:%d: HIP error %d (%s)\n", __FILE__, __LINE__, (int)e__, \
-                hipGetErrorString(e__));                                                           \
-      return MV_ERR_LAUNCH;                                                                        \
-    }                                                                                              \
+struct mv_site {
+  const char* file;
+  int line;
+};
+#define MV_HERE (mv_site{__FILE__, __LINE__})
+
+// MV_OK, or MV_ERR_LAUNCH when the runtime holds an error (with MV_DEBUG set: the error and the site `at` on stderr)
+inline int mv_check_launch(mv_site at) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return MV_OK;
+  if (getenv("MV_DEBUG"))
+    fprintf(stderr, "[myrtle_vision_hip] %s:%d: HIP error %d (%s)\n", at.file, at.line, (int)e, hipGetErrorString(e));
+  return MV_ERR_LAUNCH;
+}
+#define MV_CHECK_LAUNCH()                                           \
+  do {                                                              \
+    if (mv_check_launch(MV_HERE) != MV_OK) return MV_ERR_LAUNCH;    \
   } while (0)
+
+// Whether kernel K may be launched with `lds` bytes of dynamic LDS on the current device, raising its limit if it has to.
+// hipFuncSetAttribute acts on ONE kernel instantiation and on the CURRENT device, and a kernel starts at the default 64 KiB.  So
+// the size granted so far is remembered per (K, device): K is a template argument, every instantiation has its own table, and a
+// process that drives several GPUs -- not the one-process-per-GPU launch this library is written for, but legal -- raises the
+// limit on each.  The limit only ever grows (the raise is serialised), so a kernel that is launched with two sizes works in either
+// order and from any thread.  Without a device index in 0..31 nothing is remembered and every call raises.
+template <auto K>
+inline bool mv_grant_lds(size_t lds) {
+  static std::atomic<size_t> granted[32] = {};
+  static std::mutex raising;
+  int d = 0;
+  const bool have = hipGetDevice(&d) == hipSuccess && d >= 0 && d < 32;
+  if (have && lds <= granted[d].load(std::memory_order_acquire)) return true;
+  std::lock_guard<std::mutex> lock(raising);
+  if (have && lds <= granted[d].load(std::memory_order_relaxed)) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return false;
+  if (have) granted[d].store(lds, std::memory_order_release);
+  return true;
+}
+
+// THE way to launch a kernel with dynamic LDS: mv_launch<kernel<ARGS>>(MV_HERE, grid, block, lds, stream, kernel arguments...).
+// The kernel and the byte count are named once; the grant above and the launch cannot be paired wrongly.  MV_OK or MV_ERR_LAUNCH
+// (a failed raise does not launch).  lds == 0 adds nothing to the launch and its check.
+template <auto K, typename... A>
+inline int mv_launch(mv_site at, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  if (lds != 0 && !mv_grant_lds<K>(lds)) return MV_ERR_LAUNCH;
+  K<<<grid, block, lds, s>>>(args...);
+  return mv_check_launch(at);
+}
 
 // Argument check.  It also CLEARS the runtime's sticky last-error: hipGetLastError() reports the last error of ANY
 // earlier runtime call on this thread (e.g. the host framework probing a pointer), which MV_CHECK_LAUNCH would
