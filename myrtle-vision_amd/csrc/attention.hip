@@ -1612,9 +1612,8 @@ extern "C" int mv_attention_bwd_prep_f16(const float* dout, const float* out, vo
   MV_REQUIRE(B >= 0 && N > 0 && H > 0, MV_ERR_SHAPE);
   MV_REQUIRE(mv_aligned16(dout) && mv_aligned16(out) && mv_aligned16(dout16) && gscale && delta, MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
-  attn_bwd_prep_f16_kernel<<<B * H, 256, 0, (hipStream_t)stream>>>(dout, out, (_Float16*)dout16, delta, gscale, N, H);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<attn_bwd_prep_f16_kernel>(MV_HERE, B * H, 256, 0, (hipStream_t)stream, dout, out, (_Float16*)dout16, delta,
+                                             gscale, N, H);
 }
 
 namespace {
@@ -1639,9 +1638,9 @@ extern "C" int mv_attention_bwd_f16(const void* qkv16, const void* dout16, const
   MV_REQUIRE(mv_aligned16(qkv16) && mv_aligned16(dout16) && mv_aligned16(dqkv) && delta && lse && gscale, MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
   hipStream_t s = (hipStream_t)stream;
-  return nseg == 0   ? launch_bwd_f16<0>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s)
-         : nseg == 3 ? launch_bwd_f16<3>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s)
-                     : launch_bwd_f16<6>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s);
+  return mv_pick<0, 3, 6>(nseg, [&](auto NSEG) {
+    return launch_bwd_f16<NSEG()>(qkv16, dout16, delta, lse, gscale, dqkv, colsum, B, N, H, scale, s);
+  });
 }
 
 extern "C" int mv_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,

@@ -964,7 +964,8 @@ extern "C" int mv_attention_bwd_long_f32(const float* qkv, const float* out, con
   hipStream_t s = (hipStream_t)stream;
   constexpr int lds_dkdv = (2 * LF_STAGE + 4 * LF_BLK) * (int)sizeof(float), lds_dq = 2 * LF_STAGE * (int)sizeof(float);
   const unsigned grid = (unsigned)(nb * B * H);
-  attn_delta_long_f32_kernel<<<(unsigned)((rows * 16 + 255) / 256), 256, 0, s>>>(out, dout, delta_ws, rows, N, H);
+  if (int rc = mv_launch<attn_delta_long_f32_kernel>(MV_HERE, (unsigned)((rows * 16 + 255) / 256), 256, 0, s, out, dout, delta_ws, rows, N, H))
+    return rc;
   const int rc = mv_launch<attn_bwd_dkdv_long_f32_kernel>(MV_HERE, grid, 512, lds_dkdv, s, qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);
   if (rc != MV_OK) return rc;
   return mv_launch<attn_bwd_dq_long_f32_kernel>(MV_HERE, grid, 512, lds_dq, s, qkv, dout, lse, delta_ws, dqkv, N, H, (int)nb, scale);

@@ -705,10 +705,8 @@ int launch_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, floa
   using C = DhCfg<DH>;
   const long nqb = (N + C::WGROWS - 1) / C::WGROWS;
   MV_REQUIRE(nqb * B * H < (1L << 31), MV_ERR_SHAPE);
-  attn_fwd_kernel<DH, F16><<<(unsigned)(nqb * B * H), 256, 0, s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, H, (int)nqb,
-                                                                 scale * LOG2E);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<attn_fwd_kernel<DH, F16>>(MV_HERE, (unsigned)(nqb * B * H), 256, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N,
+                                             H, (int)nqb, scale * LOG2E);
 }
 
 template <int DH>
@@ -717,29 +715,29 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
   using C = DhCfg<DH>;
   const long nb = (N + C::WGROWS - 1) / C::WGROWS, chunks = (long)B * N * H * C::CPR;
   MV_REQUIRE(nb * B * H < (1L << 31) && (chunks + 255) / 256 < (1L << 31) && B < 65536, MV_ERR_SHAPE);
-  attn_delta_kernel<C::CPR><<<(unsigned)((chunks + 255) / 256), 256, 0, s>>>((const bf16_t*)out, (const bf16_t*)dout, delta_ws,
-                                                                            (long)B * N * H, N, H);
-  attn_bwd_dkdv_kernel<DH><<<(unsigned)(nb * B * H), 256, 0, s>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta_ws,
-                                                                              (bf16_t*)dqkv, N, H, (int)nb, scale);
-  attn_bwd_dq_kernel<DH><<<(unsigned)(nb * B * H), 256, 0, s>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta_ws,
-                                                                          (bf16_t*)dqkv, N, H, (int)nb, scale);
-  if (colsum) {
-    const int Cc = 3 * H * DH;
-    attn_colsum_kernel<<<dim3((Cc + 255) / 256, B), 256, 0, s>>>((const bf16_t*)dqkv, colsum, N, Cc);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const unsigned grid = (unsigned)(nb * B * H);
+  if (int rc = mv_launch<attn_delta_kernel<C::CPR>>(MV_HERE, (unsigned)((chunks + 255) / 256), 256, 0, s, (const bf16_t*)out,
+                                                    (const bf16_t*)dout, delta_ws, (long)B * N * H, N, H))
+    return rc;
+  if (int rc = mv_launch<attn_bwd_dkdv_kernel<DH>>(MV_HERE, grid, 256, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta_ws,
+                                                   (bf16_t*)dqkv, N, H, (int)nb, scale, nullptr, nullptr))
+    return rc;
+  const int rc = mv_launch<attn_bwd_dq_kernel<DH>>(MV_HERE, grid, 256, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta_ws,
+                                                   (bf16_t*)dqkv, N, H, (int)nb, scale, nullptr, nullptr);
+  if (rc != MV_OK || !colsum) return rc;
+  const int Cc = 3 * H * DH;
+  return mv_launch<attn_colsum_kernel>(MV_HERE, dim3((Cc + 255) / 256, B), 256, 0, s, (const bf16_t*)dqkv, colsum, N, Cc);
 }
 
 // the two F16 backward kernels (delta and gscale come from mv_attention_bwd_prep_f16); ws: the column-sum workspace or nullptr
 template <int SPLIT>
 int launch_bwd_f16(const void* qkv16, const void* dout16, const float* delta, const float* lse, const float* gscale, void* dqkv,
                    float* ws, int B, int N, int H, int nb, float scale, hipStream_t s) {
-  attn_bwd_dkdv_kernel<64, true, SPLIT><<<(unsigned)(nb * B * H), 256, 0, s>>>(
-      (const bf16_t*)qkv16, (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, nb, scale, gscale, ws);
-  attn_bwd_dq_kernel<64, true, SPLIT><<<(unsigned)(nb * B * H), 256, 0, s>>>(
-      (const bf16_t*)qkv16, (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, nb, scale, gscale, ws);
-  return MV_OK;
+  if (int rc = mv_launch<attn_bwd_dkdv_kernel<64, true, SPLIT>>(MV_HERE, (unsigned)(nb * B * H), 256, 0, s, (const bf16_t*)qkv16,
+                                                                (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, nb, scale, gscale, ws))
+    return rc;
+  return mv_launch<attn_bwd_dq_kernel<64, true, SPLIT>>(MV_HERE, (unsigned)(nb * B * H), 256, 0, s, (const bf16_t*)qkv16,
+                                                        (const bf16_t*)dout16, lse, delta, (bf16_t*)dqkv, N, H, nb, scale, gscale, ws);
 }
 
 constexpr int LROWS = DhCfg<64>::WGROWS;   // rows per workgroup of the 64-wide kernels: forward / dQ queries, dK / dV keys
@@ -797,14 +795,12 @@ extern "C" int mv_attention_bwd_long_f16(const void* qkv16, const void* dout16, 
   if (B == 0) return MV_OK;
   hipStream_t s = (hipStream_t)stream;
   float* ws = colsum ? colsum_ws : nullptr;
-  const int rc = nseg == 0   ? launch_bwd_f16<0>(qkv16, dout16, delta, lse, gscale, dqkv, ws, B, N, H, (int)nb, scale, s)
-                 : nseg == 3 ? launch_bwd_f16<3>(qkv16, dout16, delta, lse, gscale, dqkv, ws, B, N, H, (int)nb, scale, s)
-                             : launch_bwd_f16<6>(qkv16, dout16, delta, lse, gscale, dqkv, ws, B, N, H, (int)nb, scale, s);
-  if (rc != MV_OK) return rc;
-  if (colsum)
-    attn_colsum_ws_kernel<<<(unsigned)(((long)B * C + 255) / 256), 256, 0, s>>>(ws, colsum, (int)nb, (int)C, (long)B * C);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const int rc = mv_pick<0, 3, 6>(nseg, [&](auto NSEG) {
+    return launch_bwd_f16<NSEG()>(qkv16, dout16, delta, lse, gscale, dqkv, ws, B, N, H, (int)nb, scale, s);
+  });
+  if (rc != MV_OK || !colsum) return rc;
+  return mv_launch<attn_colsum_ws_kernel>(MV_HERE, (unsigned)(((long)B * C + 255) / 256), 256, 0, s, ws, colsum, (int)nb, (int)C,
+                                          (long)B * C);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -816,8 +812,7 @@ extern "C" int mv_attention_fwd_dh(const void* qkv, void* out, float* lse, int B
   MV_REQUIRE(dim_head == 32 || dim_head == 128, MV_ERR_UNSUPPORTED);
   MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(out) && lse, MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
-  return dim_head == 32 ? launch_fwd<32, false>(qkv, out, lse, B, N, H, scale, (hipStream_t)stream)
-                        : launch_fwd<128, false>(qkv, out, lse, B, N, H, scale, (hipStream_t)stream);
+  return mv_pick<32, 128>(dim_head, [&](auto DH) { return launch_fwd<DH(), false>(qkv, out, lse, B, N, H, scale, (hipStream_t)stream); });
 }
 
 extern "C" int mv_attention_bwd_dh(const void* qkv, const void* out, const void* dout, const float* lse, float* delta_ws,
@@ -826,6 +821,7 @@ extern "C" int mv_attention_bwd_dh(const void* qkv, const void* out, const void*
   MV_REQUIRE(dim_head == 32 || dim_head == 128, MV_ERR_UNSUPPORTED);
   MV_REQUIRE(mv_aligned16(qkv) && mv_aligned16(out) && mv_aligned16(dout) && mv_aligned16(dqkv) && lse && delta_ws, MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
-  return dim_head == 32 ? launch_bwd<32>(qkv, out, dout, lse, delta_ws, dqkv, colsum, B, N, H, scale, (hipStream_t)stream)
-                        : launch_bwd<128>(qkv, out, dout, lse, delta_ws, dqkv, colsum, B, N, H, scale, (hipStream_t)stream);
+  return mv_pick<32, 128>(dim_head, [&](auto DH) {
+    return launch_bwd<DH()>(qkv, out, dout, lse, delta_ws, dqkv, colsum, B, N, H, scale, (hipStream_t)stream);
+  });
 }

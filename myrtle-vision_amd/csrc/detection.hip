@@ -586,17 +586,14 @@ inline bool det_dims_ok(int B, int Q, int C1) { return B > 0 && Q > 0 && C1 >= 2
 
 }  // namespace
 
-#define S_ ((hipStream_t)stream)
-
 extern "C" int mv_det_heads_fwd(const float* x, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
                                 float* logits, float* boxes, int B, int T, int Q, int D, int C1, mv_stream_t stream) {
   MV_REQUIRE(det_dims_ok(B, Q, C1) && T >= Q && D > 0 && C1 + 4 <= DET_NMAX, MV_ERR_SHAPE);
   const size_t lds = (size_t)DET_ROWS * D * sizeof(float);
   MV_REQUIRE(lds <= DET_LDS_LIMIT, MV_ERR_UNSUPPORTED);
   const long M = (long)B * Q;
-  det_heads_fwd_kernel<<<mv_cdiv(M, DET_ROWS), 256, lds, S_>>>(x, w_cls, b_cls, w_box, b_box, logits, boxes, M, T, Q, D, C1);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_heads_fwd_kernel>(MV_HERE, mv_cdiv(M, DET_ROWS), 256, lds, (hipStream_t)stream, x, w_cls, b_cls, w_box,
+                                         b_box, logits, boxes, M, T, Q, D, C1);
 }
 
 extern "C" size_t mv_det_heads_bwd_workspace_bytes(int B, int Q, int D, int C1) {
@@ -611,15 +608,18 @@ extern "C" int mv_det_heads_bwd(const float* x, const float* w_cls, const float*
   MV_REQUIRE(workspace_bytes >= mv_det_heads_bwd_workspace_bytes(B, Q, D, C1) && mv_aligned16(workspace), MV_ERR_ALIGN);
   const long M = (long)B * Q;
   const int N = C1 + 4;
-  if (dx) det_heads_dx_kernel<<<mv_cdiv(M, DET_ROWS), 256, 0, S_>>>(w_cls, w_box, boxes, dlogits, dboxes, dx, M, T, Q, D, C1);
+  hipStream_t s = (hipStream_t)stream;
+  if (dx)
+    if (int rc = mv_launch<det_heads_dx_kernel>(MV_HERE, mv_cdiv(M, DET_ROWS), 256, 0, s, w_cls, w_box, boxes, dlogits, dboxes, dx, M, T, Q, D, C1))
+      return rc;
   const int S = det_slabs(M);
   const int rows_per_slab = (int)((M + S - 1) / S);
   float* partial = (float*)workspace;
-  det_heads_dw_kernel<<<dim3(mv_cdiv(D, 256), mv_cdiv(N, DET_DW_NT), S), 256, 0, S_>>>(x, boxes, dlogits, dboxes, partial, M,
-                                                                                      rows_per_slab, T, Q, D, C1);
-  det_heads_dw_sum_kernel<<<mv_cdiv((long)N * (D + 1), 256), 256, 0, S_>>>(partial, S, dw_cls, db_cls, dw_box, db_box, D, C1);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  if (int rc = mv_launch<det_heads_dw_kernel>(MV_HERE, dim3(mv_cdiv(D, 256), mv_cdiv(N, DET_DW_NT), S), 256, 0, s, x, boxes, dlogits, dboxes,
+                                              partial, M, rows_per_slab, T, Q, D, C1))
+    return rc;
+  return mv_launch<det_heads_dw_sum_kernel>(MV_HERE, mv_cdiv((long)N * (D + 1), 256), 256, 0, s, partial, S, dw_cls, db_cls, dw_box, db_box,
+                                            D, C1);
 }
 
 extern "C" int mv_det_append_fwd(const float* x, const float* det, const float* pos, float* out, int B, int T0, int Q, int D,
@@ -627,9 +627,8 @@ extern "C" int mv_det_append_fwd(const float* x, const float* det, const float* 
   MV_REQUIRE(B > 0 && T0 > 0 && Q > 0 && D > 0, MV_ERR_SHAPE);
   const long total = (long)B * (T0 + Q) * D;
   MV_REQUIRE(total / 256 < 0x7fffffffl, MV_ERR_SHAPE);
-  det_append_fwd_kernel<<<mv_cdiv(total, 256), 256, 0, S_>>>(x, det, pos, out, total, T0, Q, D);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_append_fwd_kernel>(MV_HERE, mv_cdiv(total, 256), 256, 0, (hipStream_t)stream, x, det, pos, out, total, T0, Q,
+                                          D);
 }
 
 extern "C" int mv_det_append_bwd(const float* dout, float* dx, float* ddet, float* dpos, int B, int T0, int Q, int D,
@@ -637,18 +636,16 @@ extern "C" int mv_det_append_bwd(const float* dout, float* dx, float* ddet, floa
   MV_REQUIRE(B > 0 && T0 > 0 && Q > 0 && D > 0, MV_ERR_SHAPE);
   const long total = (long)B * T0 * D + (long)Q * D;
   MV_REQUIRE(total / 256 < 0x7fffffffl, MV_ERR_SHAPE);
-  det_append_bwd_kernel<<<mv_cdiv(total, 256), 256, 0, S_>>>(dout, dx, ddet, dpos, B, T0, Q, D);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_append_bwd_kernel>(MV_HERE, mv_cdiv(total, 256), 256, 0, (hipStream_t)stream, dout, dx, ddet, dpos, B, T0, Q,
+                                          D);
 }
 
 extern "C" int mv_det_cost(const float* logits, const float* boxes, const int64_t* labels, const float* tboxes,
                            const int32_t* toff, float* out, float cost_class, float cost_bbox, float cost_giou, int B, int Q,
                            int C1, mv_stream_t stream) {
   MV_REQUIRE(det_dims_ok(B, Q, C1), MV_ERR_SHAPE);
-  det_cost_kernel<<<dim3(Q, B), 64, 0, S_>>>(logits, boxes, labels, tboxes, toff, out, cost_class, cost_bbox, cost_giou, Q, C1);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_cost_kernel>(MV_HERE, dim3(Q, B), 64, 0, (hipStream_t)stream, logits, boxes, labels, tboxes, toff, out,
+                                    cost_class, cost_bbox, cost_giou, Q, C1);
 }
 
 extern "C" int mv_det_match(const float* cost, const int32_t* toff, int32_t* match, int32_t* status, int B, int Q, int max_t,
@@ -659,17 +656,15 @@ extern "C" int mv_det_match(const float* cost, const int32_t* toff, int32_t* mat
   const size_t state = det_match_state_bytes(nr_max, nc_max);
   size_t cap = (DET_LDS_LIMIT - state) / sizeof(float);
   if ((size_t)Q * max_t < cap) cap = (size_t)Q * max_t;
-  det_match_kernel<<<B, 64, state + cap * sizeof(float), S_>>>(cost, toff, match, status, Q, max_t, nr_max, nc_max, (int)cap);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_match_kernel>(MV_HERE, B, 64, state + cap * sizeof(float), (hipStream_t)stream, cost, toff, match, status, Q,
+                                     max_t, nr_max, nc_max, (int)cap);
 }
 
 extern "C" int mv_det_assign(const int32_t* match, const int64_t* labels, const float* tboxes, int64_t* tgt_class, float* tgt_box,
                              long n, long ntargets, int no_object, mv_stream_t stream) {
   MV_REQUIRE(n > 0 && n < (1l << 30) && ntargets >= 0 && no_object >= 0, MV_ERR_SHAPE);
-  det_assign_kernel<<<mv_cdiv(n, 256), 256, 0, S_>>>(match, labels, tboxes, tgt_class, tgt_box, n, ntargets, no_object);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_assign_kernel>(MV_HERE, mv_cdiv(n, 256), 256, 0, (hipStream_t)stream, match, labels, tboxes, tgt_class,
+                                      tgt_box, n, ntargets, no_object);
 }
 
 extern "C" int mv_det_loss_fwd(const float* logits, const float* boxes, const int64_t* tgt_class, const float* tgt_box,
@@ -677,10 +672,8 @@ extern "C" int mv_det_loss_fwd(const float* logits, const float* boxes, const in
                                int Q, int C1, mv_stream_t stream) {
   MV_REQUIRE(det_dims_ok(B, Q, C1), MV_ERR_SHAPE);
   MV_REQUIRE((size_t)B * sizeof(int) <= DET_LDS_LIMIT / 2, MV_ERR_UNSUPPORTED);
-  det_loss_fwd_kernel<<<1, 256, (size_t)B * sizeof(int), S_>>>(logits, boxes, tgt_class, tgt_box, weight, tcount, lse, stats,
-                                                               inv_num_boxes, B, Q, C1);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_loss_fwd_kernel>(MV_HERE, 1, 256, (size_t)B * sizeof(int), (hipStream_t)stream, logits, boxes, tgt_class,
+                                        tgt_box, weight, tcount, lse, stats, inv_num_boxes, B, Q, C1);
 }
 
 extern "C" int mv_det_loss_bwd(const float* logits, const float* boxes, const int64_t* tgt_class, const float* tgt_box,
@@ -689,17 +682,14 @@ extern "C" int mv_det_loss_bwd(const float* logits, const float* boxes, const in
                                mv_stream_t stream) {
   MV_REQUIRE(det_dims_ok(B, Q, C1), MV_ERR_SHAPE);
   const long n = (long)B * Q;
-  det_loss_bwd_kernel<<<mv_cdiv(n, 256), 256, 0, S_>>>(logits, boxes, tgt_class, tgt_box, weight, lse, stats, g_ce, g_bbox, g_giou,
-                                                       dlogits, dboxes, inv_num_boxes, n, C1);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_loss_bwd_kernel>(MV_HERE, mv_cdiv(n, 256), 256, 0, (hipStream_t)stream, logits, boxes, tgt_class, tgt_box,
+                                        weight, lse, stats, g_ce, g_bbox, g_giou, dlogits, dboxes, inv_num_boxes, n, C1);
 }
 
 extern "C" int mv_det_postprocess(const float* logits, const float* boxes, const float* sizes, float* scores, int64_t* labels,
                                   float* out_boxes, int B, int Q, int C1, mv_stream_t stream) {
   MV_REQUIRE(det_dims_ok(B, Q, C1), MV_ERR_SHAPE);
   const long n = (long)B * Q;
-  det_postprocess_kernel<<<mv_cdiv(n, 256), 256, 0, S_>>>(logits, boxes, sizes, scores, labels, out_boxes, n, Q, C1);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<det_postprocess_kernel>(MV_HERE, mv_cdiv(n, 256), 256, 0, (hipStream_t)stream, logits, boxes, sizes, scores,
+                                           labels, out_boxes, n, Q, C1);
 }

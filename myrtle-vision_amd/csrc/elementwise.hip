@@ -822,8 +822,6 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 
 }  // namespace
 
-#define S_ ((hipStream_t)stream)
-
 extern "C" int mv_version(void) { return 100; }
 extern "C" const char* mv_error_string(int code) {
   switch (code) {
@@ -842,37 +840,25 @@ extern "C" int mv_patchify(const float* img, void* out, int out_dtype, int B, in
   MV_REQUIRE(B >= 0 && C > 0 && p > 0 && H % p == 0 && W % p == 0, MV_ERR_SHAPE);
   MV_REQUIRE(out_dtype == MV_F32 || out_dtype == MV_BF16, MV_ERR_UNSUPPORTED);
   if (B == 0) return MV_OK;
-  if (C == 3 && p % 4 == 0 && W % 4 == 0 && mv_aligned16(img)) {
-    const long items = (long)B * H * (W / 4);
-    if (out_dtype == MV_F32)
-      patchify_kernel<float, 3><<<ew_grid(items), 256, 0, S_>>>(img, (float*)out, B, H, W, p);
-    else
-      patchify_kernel<bf16_t, 3><<<ew_grid(items), 256, 0, S_>>>(img, (bf16_t*)out, B, H, W, p);
-  } else {
-    const long n = (long)B * C * H * W;
-    if (out_dtype == MV_F32)
-      patchify_generic_kernel<float><<<ew_grid(n), 256, 0, S_>>>(img, (float*)out, B, C, H, W, p);
-    else
-      patchify_generic_kernel<bf16_t><<<ew_grid(n), 256, 0, S_>>>(img, (bf16_t*)out, B, C, H, W, p);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(out_dtype, [&](auto D) {
+    using T = mv_elem_t<D()>;
+    if (C == 3 && p % 4 == 0 && W % 4 == 0 && mv_aligned16(img))
+      return mv_launch<patchify_kernel<T, 3>>(MV_HERE, ew_grid((long)B * H * (W / 4)), 256, 0, (hipStream_t)stream, img, (T*)out, B, H, W, p);
+    return mv_launch<patchify_generic_kernel<T>>(MV_HERE, ew_grid((long)B * C * H * W), 256, 0, (hipStream_t)stream, img, (T*)out, B, C, H, W, p);
+  });
 }
 
 extern "C" int mv_embed_cls(const float* cls, const float* pos, float* x, int B, int T, int D, mv_stream_t stream) {
   MV_REQUIRE(B >= 0 && T > 0 && D > 0, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  embed_cls_kernel<<<ew_grid((long)B * D), 256, 0, S_>>>(cls, pos, x, B, T, D);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<embed_cls_kernel>(MV_HERE, ew_grid((long)B * D), 256, 0, (hipStream_t)stream, cls, pos, x, B, T, D);
 }
 
 extern "C" int mv_embed_bwd(const float* dx, float* dpos, float* dcls, int accumulate, int B, int T, int D,
                             mv_stream_t stream) {
   MV_REQUIRE(B >= 0 && T > 0 && D > 0, MV_ERR_SHAPE);
-  embed_bwd_kernel<<<ew_grid((long)T * D), 256, 0, S_>>>(dx, dpos, dcls, accumulate, B, T, D);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<embed_bwd_kernel>(MV_HERE, ew_grid((long)T * D), 256, 0, (hipStream_t)stream, dx, dpos, dcls, accumulate, B, T,
+                                     D);
 }
 
 // Backward of the embedding assembly in ONE pass over dx [B, T, D] (round 4; replaces embed_bwd_kernel + gather_patch_rows_kernel:
@@ -927,12 +913,10 @@ extern "C" int mv_embed_bwd_gather(const float* dx, void* dy, int dy_dtype, floa
   MV_REQUIRE(mv_aligned16(dx) && mv_aligned16(dy) && mv_aligned16(dpos) && mv_aligned16(dcls), MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
   const int grid = T * ((D + 127) / 128);
-  if (dy_dtype == MV_F32)
-    embed_bwd_gather_kernel<float><<<grid, 256, 0, S_>>>(dx, (float*)dy, dpos, dcls, B, T, D);
-  else
-    embed_bwd_gather_kernel<bf16_t><<<grid, 256, 0, S_>>>(dx, (bf16_t*)dy, dpos, dcls, B, T, D);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(dy_dtype, [&](auto DTYPE) {
+    using DT = mv_elem_t<DTYPE()>;
+    return mv_launch<embed_bwd_gather_kernel<DT>>(MV_HERE, grid, 256, 0, (hipStream_t)stream, dx, (DT*)dy, dpos, dcls, B, T, D);
+  });
 }
 
 extern "C" int mv_gather_patch_rows(const float* src, void* dst, int dst_dtype, int B, int T, int D,
@@ -941,14 +925,10 @@ extern "C" int mv_gather_patch_rows(const float* src, void* dst, int dst_dtype, 
   MV_REQUIRE(mv_aligned16(src) && mv_aligned16(dst), MV_ERR_ALIGN);
   if (B == 0) return MV_OK;
   const long n = (long)B * (T - 1) * (D / 4);
-  if (dst_dtype == MV_F32)
-    gather_patch_rows_kernel<float><<<ew_grid(n), 256, 0, S_>>>(src, (float*)dst, B, T, D);
-  else if (dst_dtype == MV_BF16)
-    gather_patch_rows_kernel<bf16_t><<<ew_grid(n), 256, 0, S_>>>(src, (bf16_t*)dst, B, T, D);
-  else
-    return MV_ERR_UNSUPPORTED;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(dst_dtype, [&](auto DTYPE) {
+    using DT = mv_elem_t<DTYPE()>;
+    return mv_launch<gather_patch_rows_kernel<DT>>(MV_HERE, ew_grid(n), 256, 0, (hipStream_t)stream, src, (DT*)dst, B, T, D);
+  });
 }
 
 extern "C" int mv_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, mv_stream_t stream) {
@@ -956,18 +936,18 @@ extern "C" int mv_cast(const void* src, int src_dtype, void* dst, int dst_dtype,
   if (n == 0) return MV_OK;
   MV_REQUIRE(mv_aligned16(src) && mv_aligned16(dst), MV_ERR_ALIGN);
   const int grid = ew_grid((n + 3) / 4);
-  if (src_dtype == MV_F32 && dst_dtype == MV_BF16)
-    cast_kernel<float, bf16_t><<<grid, 256, 0, S_>>>((const float*)src, (bf16_t*)dst, n);
-  else if (src_dtype == MV_BF16 && dst_dtype == MV_F32)
-    cast_kernel<bf16_t, float><<<grid, 256, 0, S_>>>((const bf16_t*)src, (float*)dst, n);
-  else if (src_dtype == MV_F32 && dst_dtype == MV_F32)
-    cast_kernel<float, float><<<grid, 256, 0, S_>>>((const float*)src, (float*)dst, n);
-  else if (src_dtype == MV_F32 && dst_dtype == MV_F16)
-    cast_f16_kernel<<<grid, 256, 0, S_>>>((const float*)src, (_Float16*)dst, n);
-  else
-    return MV_ERR_UNSUPPORTED;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (src_dtype == MV_F32 && dst_dtype == MV_F16) return mv_launch<cast_f16_kernel>(MV_HERE, grid, 256, 0, s, (const float*)src, (_Float16*)dst, n);
+  // the pairs that are built: fp32 -> fp32 | bf16, bf16 -> fp32
+  return mv_pick<MV_F32, MV_BF16>(src_dtype, [&](auto S) {
+    using ST = mv_elem_t<S()>;
+    auto go = [&](auto D) {
+      using DT = mv_elem_t<D()>;
+      return mv_launch<cast_kernel<ST, DT>>(MV_HERE, grid, 256, 0, s, (const ST*)src, (DT*)dst, n);
+    };
+    if constexpr (S() == MV_F32) return mv_pick<MV_F32, MV_BF16>(dst_dtype, go);
+    else return mv_pick<MV_F32>(dst_dtype, go);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1110,19 +1090,13 @@ int launch_split_ex(const float* x, long ldx, const float* h, long ldh, int op, 
   dim3 grid(mv_cdiv(cols / 4, 256), mv_cdiv(rows, rpp));
   float* partial = colsum ? workspace : nullptr;
   const long ldo = (long)NSEG * cols, seg = cols;
-  if (op == 0)
-    split3_ex_kernel<0, NSEG><<<grid, 256, 0, S_>>>(x, ldx, h, ldh, (bf16_t*)out, ldo, seg, rows, cols / 4, rpp, partial);
-  else if (op == 1)
-    split3_ex_kernel<1, NSEG><<<grid, 256, 0, S_>>>(x, ldx, h, ldh, (bf16_t*)out, ldo, seg, rows, cols / 4, rpp, partial);
-  else
-    split3_ex_kernel<2, NSEG><<<grid, 256, 0, S_>>>(x, ldx, h, ldh, (bf16_t*)out, ldo, seg, rows, cols / 4, rpp, partial);
-  MV_CHECK_LAUNCH();
-  if (colsum) {
-    mv_reduce_rows_kernel<<<mv_reduce_rows_grid(cols), 1024, 0, S_>>>(workspace, (int)grid.y, cols, (long)cols, colsum, colsum,
-                                                                        colsum, cols, cols, 0);
-    MV_CHECK_LAUNCH();
-  }
-  return MV_OK;
+  const int rc = mv_pick<0, 1, 2>(op, [&](auto OP) {
+    return mv_launch<split3_ex_kernel<OP(), NSEG>>(MV_HERE, grid, 256, 0, (hipStream_t)stream, x, ldx, h, ldh, (bf16_t*)out, ldo, seg, rows,
+                                                   cols / 4, rpp, partial);
+  });
+  if (rc != MV_OK || !colsum) return rc;
+  return mv_launch<mv_reduce_rows_kernel>(MV_HERE, mv_reduce_rows_grid(cols), 1024, 0, (hipStream_t)stream, workspace, (int)grid.y, cols,
+                                          (long)cols, colsum, colsum, colsum, cols, cols, 0);
 }
 
 template <int NSEG>
@@ -1132,12 +1106,9 @@ int launch_split(const float* x, long ldx, void* out, long ldo, long seg, long r
   MV_REQUIRE(cols % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && seg % 4 == 0 && ldx >= cols && ldo >= cols, MV_ERR_ALIGN);
   MV_REQUIRE(mv_aligned16(x) && mv_aligned16(out), MV_ERR_ALIGN);
   const int grid = ew_grid(rows * (cols / 4));
-  if (role == 0)
-    split3_kernel<0, NSEG><<<grid, 256, 0, S_>>>(x, ldx, (bf16_t*)out, ldo, seg, rows, cols / 4);
-  else
-    split3_kernel<1, NSEG><<<grid, 256, 0, S_>>>(x, ldx, (bf16_t*)out, ldo, seg, rows, cols / 4);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<0, 1>(role, [&](auto ROLE) {
+    return mv_launch<split3_kernel<ROLE(), NSEG>>(MV_HERE, grid, 256, 0, (hipStream_t)stream, x, ldx, (bf16_t*)out, ldo, seg, rows, cols / 4);
+  });
 }
 }  // namespace
 
@@ -1169,15 +1140,11 @@ extern "C" int mv_weight_prep(const float* w, void* w_bf16, int ldw, void* wt_bf
   const bool pairs = (!w_bf16 || ((ldw & 1) == 0 && (reinterpret_cast<uintptr_t>(w_bf16) & 3) == 0)) &&
                      (!wt_bf16 || ((ldt & 1) == 0 && (reinterpret_cast<uintptr_t>(wt_bf16) & 3) == 0)) &&
                      (reinterpret_cast<uintptr_t>(w) & 7) == 0;
-  if (pairs) {
-    dim3 grid(mv_cdiv(cols, 64), mv_cdiv(rows, 64));
-    weight_prep64_kernel<<<grid, 256, 0, S_>>>(w, (bf16_t*)w_bf16, ldw, (bf16_t*)wt_bf16, ldt, R, C);
-  } else {
-    dim3 grid(mv_cdiv(cols, 32), mv_cdiv(rows, 32));
-    weight_prep_kernel<<<grid, 256, 0, S_>>>(w, (bf16_t*)w_bf16, ldw, (bf16_t*)wt_bf16, ldt, R, C);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  if (pairs)
+    return mv_launch<weight_prep64_kernel>(MV_HERE, dim3(mv_cdiv(cols, 64), mv_cdiv(rows, 64)), 256, 0, (hipStream_t)stream, w, (bf16_t*)w_bf16,
+                                           ldw, (bf16_t*)wt_bf16, ldt, R, C);
+  return mv_launch<weight_prep_kernel>(MV_HERE, dim3(mv_cdiv(cols, 32), mv_cdiv(rows, 32)), 256, 0, (hipStream_t)stream, w, (bf16_t*)w_bf16, ldw,
+                                       (bf16_t*)wt_bf16, ldt, R, C);
 }
 
 extern "C" int mv_weight_prep_batch(const mv_weight_prep_item* items_device, int count, int total_blocks,
@@ -1185,21 +1152,16 @@ extern "C" int mv_weight_prep_batch(const mv_weight_prep_item* items_device, int
   MV_REQUIRE(count >= 0 && total_blocks >= 0 && (count == 0) == (total_blocks == 0), MV_ERR_SHAPE);
   if (count == 0) return MV_OK;
   MV_REQUIRE(items_device != nullptr, MV_ERR_SHAPE);
-  weight_prep_batch_kernel<<<total_blocks, 256, 0, S_>>>(items_device, count);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<weight_prep_batch_kernel>(MV_HERE, total_blocks, 256, 0, (hipStream_t)stream, items_device, count);
 }
 
 extern "C" int mv_weight_split(const float* w, void* fwd, void* dx, int R, int C, int nseg, mv_stream_t stream) {
   MV_REQUIRE(R > 0 && C > 0 && R % 2 == 0 && C % 2 == 0 && (nseg == 3 || nseg == 6) && (fwd || dx), MV_ERR_SHAPE);
   MV_REQUIRE(mv_aligned16(w) && (!fwd || mv_aligned16(fwd)) && (!dx || mv_aligned16(dx)), MV_ERR_ALIGN);
   const dim3 grid(mv_cdiv(C, 64), mv_cdiv(R, 64));
-  if (nseg == 3)
-    weight_split_kernel<3><<<grid, 256, 0, S_>>>(w, (bf16_t*)fwd, (bf16_t*)dx, R, C);
-  else
-    weight_split_kernel<6><<<grid, 256, 0, S_>>>(w, (bf16_t*)fwd, (bf16_t*)dx, R, C);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<3, 6>(nseg, [&](auto NSEG) {
+    return mv_launch<weight_split_kernel<NSEG()>>(MV_HERE, grid, 256, 0, (hipStream_t)stream, w, (bf16_t*)fwd, (bf16_t*)dx, R, C);
+  });
 }
 
 extern "C" int mv_split_f8c(const float* x, long ldx, void* out, long ldo_bytes, long rows, int cols, int role, int exp_hi,
@@ -1210,56 +1172,42 @@ extern "C" int mv_split_f8c(const float* x, long ldx, void* out, long ldo_bytes,
   MV_REQUIRE(mv_aligned16(x) && mv_aligned16(out), MV_ERR_ALIGN);
   const int grid = ew_grid(rows * (cols / 4));
   const float s_hi = ldexpf(1.0f, exp_hi), s_lo = ldexpf(1.0f, exp_hi + 8);
-  if (role == 0)
-    split_f8c_kernel<0><<<grid, 256, 0, S_>>>(x, ldx, (unsigned char*)out, ldo_bytes, rows, cols / 4, s_hi, s_lo);
-  else
-    split_f8c_kernel<1><<<grid, 256, 0, S_>>>(x, ldx, (unsigned char*)out, ldo_bytes, rows, cols / 4, s_hi, s_lo);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<0, 1>(role, [&](auto ROLE) {
+    return mv_launch<split_f8c_kernel<ROLE()>>(MV_HERE, grid, 256, 0, (hipStream_t)stream, x, ldx, (unsigned char*)out, ldo_bytes, rows, cols / 4,
+                                               s_hi, s_lo);
+  });
 }
 
 extern "C" int mv_gelu_fwd(const void* x, void* y, int dtype, long n, mv_stream_t stream) {
   MV_REQUIRE(n >= 0, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
-  if (dtype == MV_F32)
-    gelu_fwd_kernel<float><<<ew_grid(n), 256, 0, S_>>>((const float*)x, (float*)y, n);
-  else if (dtype == MV_BF16)
-    gelu_fwd_kernel<bf16_t><<<ew_grid(n), 256, 0, S_>>>((const bf16_t*)x, (bf16_t*)y, n);
-  else
-    return MV_ERR_UNSUPPORTED;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(dtype, [&](auto D) {
+    using T = mv_elem_t<D()>;
+    return mv_launch<gelu_fwd_kernel<T>>(MV_HERE, ew_grid(n), 256, 0, (hipStream_t)stream, (const T*)x, (T*)y, n);
+  });
 }
 
 extern "C" int mv_gelu_bwd(const void* x, const void* dy, void* dx, int dtype, long n, mv_stream_t stream) {
   MV_REQUIRE(n >= 0, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
-  if (dtype == MV_F32)
-    gelu_bwd_kernel<float><<<ew_grid(n), 256, 0, S_>>>((const float*)x, (const float*)dy, (float*)dx, n);
-  else if (dtype == MV_BF16)
-    gelu_bwd_kernel<bf16_t><<<ew_grid(n), 256, 0, S_>>>((const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n);
-  else
-    return MV_ERR_UNSUPPORTED;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(dtype, [&](auto D) {
+    using T = mv_elem_t<D()>;
+    return mv_launch<gelu_bwd_kernel<T>>(MV_HERE, ew_grid(n), 256, 0, (hipStream_t)stream, (const T*)x, (const T*)dy, (T*)dx, n);
+  });
 }
 
 extern "C" int mv_add_f32(const float* a, const float* b, float* out, long n, mv_stream_t stream) {
   MV_REQUIRE(n >= 0, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
   MV_REQUIRE(mv_aligned16(a) && mv_aligned16(b) && mv_aligned16(out), MV_ERR_ALIGN);
-  add_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(a, b, out, n);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<add_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, a, b, out, n);
 }
 
 extern "C" int mv_quant_float(const float* x, float* y, long n, int exp_bits, int man_bits, mv_stream_t stream) {
   MV_REQUIRE(n >= 0 && exp_bits >= 2 && exp_bits <= 8 && man_bits >= 0 && man_bits <= 22, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
   MV_REQUIRE(mv_aligned16(x) && mv_aligned16(y), MV_ERR_ALIGN);
-  quant_float_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(x, y, n, exp_bits, man_bits);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<quant_float_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, x, y, n, exp_bits, man_bits);
 }
 
 // float_quantize(5, 10) written as IEEE half: every value of that format (subnormals included, saturation at 65504) is
@@ -1280,9 +1228,7 @@ extern "C" int mv_quant_float_f16(const float* x, void* y, long n, mv_stream_t s
   MV_REQUIRE(n >= 0, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
   MV_REQUIRE(mv_aligned16(x) && mv_aligned16(y), MV_ERR_ALIGN);
-  quant_float_f16_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(x, (_Float16*)y, n);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<quant_float_f16_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, x, (_Float16*)y, n);
 }
 
 extern "C" int mv_quant_fixed(const float* x, float* y, long n, int wl, int fl, int clamp, int symmetric,
@@ -1292,37 +1238,15 @@ extern "C" int mv_quant_fixed(const float* x, float* y, long n, int wl, int fl, 
   const float scale = ldexpf(1.f, fl), inv = ldexpf(1.f, -fl);
   float tmax = ldexpf(1.f, wl - fl - 1) - inv, tmin = -ldexpf(1.f, wl - fl - 1);
   if (symmetric) tmin += inv;
-  quant_fixed_kernel<<<ew_grid(n), 256, 0, S_>>>(x, y, n, scale, inv, tmin, tmax, clamp);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<quant_fixed_kernel>(MV_HERE, ew_grid(n), 256, 0, (hipStream_t)stream, x, y, n, scale, inv, tmin, tmax, clamp);
 }
 
 extern "C" int mv_quant_affine(const float* x, float* y, long n, float scale, int zero_point, int qmin, int qmax,
                                mv_stream_t stream) {
   MV_REQUIRE(n >= 0 && scale > 0.f && qmin < qmax, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
-  quant_affine_kernel<<<ew_grid(n), 256, 0, S_>>>(x, y, n, scale, 1.0f / scale, zero_point, qmin, qmax);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
-}
-
-template <typename XT>
-static int launch_quant_codes(const XT* x, void* codes, long rows, int cols, int ld, float inv, int zero_point, int qmin,
-                              int qmax, int pre_op, hipStream_t s) {
-  const bool vec = (cols & 3) == 0 && (ld & 3) == 0 && mv_aligned16(x) && (reinterpret_cast<uintptr_t>(codes) & 7) == 0;
-  if (vec) {
-    const int grid = rows < 65536 ? (int)rows : 65536;
-    if (pre_op)
-      quant_affine_codes_vec_kernel<1, XT><<<grid, 256, 0, s>>>(x, (bf16_t*)codes, rows, cols, ld, inv, zero_point, qmin, qmax);
-    else
-      quant_affine_codes_vec_kernel<0, XT><<<grid, 256, 0, s>>>(x, (bf16_t*)codes, rows, cols, ld, inv, zero_point, qmin, qmax);
-  } else if (pre_op) {
-    quant_affine_codes_kernel<1, XT><<<ew_grid(rows * ld), 256, 0, s>>>(x, (bf16_t*)codes, rows, cols, ld, inv, zero_point, qmin, qmax);
-  } else {
-    quant_affine_codes_kernel<0, XT><<<ew_grid(rows * ld), 256, 0, s>>>(x, (bf16_t*)codes, rows, cols, ld, inv, zero_point, qmin, qmax);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<quant_affine_kernel>(MV_HERE, ew_grid(n), 256, 0, (hipStream_t)stream, x, y, n, scale, 1.0f / scale, zero_point,
+                                        qmin, qmax);
 }
 
 extern "C" int mv_quant_affine_codes(const void* x, int x_dtype, void* codes, long rows, int cols, int ld, float scale,
@@ -1332,9 +1256,17 @@ extern "C" int mv_quant_affine_codes(const void* x, int x_dtype, void* codes, lo
   MV_REQUIRE((pre_op == 0 || pre_op == 1) && (x_dtype == MV_F32 || x_dtype == MV_BF16), MV_ERR_UNSUPPORTED);
   if (rows == 0) return MV_OK;
   const float inv = 1.0f / scale;
-  if (x_dtype == MV_F32)
-    return launch_quant_codes((const float*)x, codes, rows, cols, ld, inv, zero_point, qmin, qmax, pre_op, S_);
-  return launch_quant_codes((const bf16_t*)x, codes, rows, cols, ld, inv, zero_point, qmin, qmax, pre_op, S_);
+  const bool vec = (cols & 3) == 0 && (ld & 3) == 0 && mv_aligned16(x) && (reinterpret_cast<uintptr_t>(codes) & 7) == 0;
+  return mv_pick<MV_F32, MV_BF16>(x_dtype, [&](auto D) {
+    return mv_pick<0, 1>(pre_op, [&](auto PRE) {
+      using T = mv_elem_t<decltype(D)::value>;
+      if (vec)
+        return mv_launch<quant_affine_codes_vec_kernel<PRE(), T>>(MV_HERE, rows < 65536 ? (int)rows : 65536, 256, 0, (hipStream_t)stream,
+                                                                  (const T*)x, (bf16_t*)codes, rows, cols, ld, inv, zero_point, qmin, qmax);
+      return mv_launch<quant_affine_codes_kernel<PRE(), T>>(MV_HERE, ew_grid(rows * ld), 256, 0, (hipStream_t)stream, (const T*)x,
+                                                            (bf16_t*)codes, rows, cols, ld, inv, zero_point, qmin, qmax);
+    });
+  });
 }
 
 extern "C" int mv_quant_affine_i8(const void* x, int x_dtype, void* codes, long rows, int cols, int ld, float scale,
@@ -1346,22 +1278,17 @@ extern "C" int mv_quant_affine_i8(const void* x, int x_dtype, void* codes, long 
   if (rows == 0) return MV_OK;
   const float inv = 1.0f / scale;
   const long n = rows * (long)cols;
-  if (ld == cols && (n & 1023) == 0 && mv_aligned16(x)) {         // no padding columns: the coalesced flat form
-    const int fgrid = ew_grid(n >> 10, 4);
-#define MV_QI8F(PRE_, T_) quant_affine_i8_flat_kernel<PRE_, T_><<<fgrid, 256, 0, S_>>>((const T_*)x, (unsigned*)codes, n, inv, zero_point)
-    if (x_dtype == MV_F32) { if (pre_op) MV_QI8F(1, float); else MV_QI8F(0, float); }
-    else { if (pre_op) MV_QI8F(1, bf16_t); else MV_QI8F(0, bf16_t); }
-#undef MV_QI8F
-    MV_CHECK_LAUNCH();
-    return MV_OK;
-  }
-  const int grid = rows < 4096 ? (int)rows : 4096;
-#define MV_QI8(PRE_, T_) quant_affine_i8_kernel<PRE_, T_><<<grid, 256, 0, S_>>>((const T_*)x, (int8_t*)codes, rows, cols, ld, inv, zero_point)
-  if (x_dtype == MV_F32) { if (pre_op) MV_QI8(1, float); else MV_QI8(0, float); }
-  else { if (pre_op) MV_QI8(1, bf16_t); else MV_QI8(0, bf16_t); }
-#undef MV_QI8
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const bool flat = ld == cols && (n & 1023) == 0 && mv_aligned16(x);         // no padding columns: the coalesced flat form
+  return mv_pick<MV_F32, MV_BF16>(x_dtype, [&](auto D) {
+    return mv_pick<0, 1>(pre_op, [&](auto PRE) {
+      using T = mv_elem_t<decltype(D)::value>;
+      if (flat)
+        return mv_launch<quant_affine_i8_flat_kernel<PRE(), T>>(MV_HERE, ew_grid(n >> 10, 4), 256, 0, (hipStream_t)stream, (const T*)x,
+                                                                (unsigned*)codes, n, inv, zero_point);
+      return mv_launch<quant_affine_i8_kernel<PRE(), T>>(MV_HERE, rows < 4096 ? (int)rows : 4096, 256, 0, (hipStream_t)stream, (const T*)x,
+                                                         (int8_t*)codes, rows, cols, ld, inv, zero_point);
+    });
+  });
 }
 
 extern "C" int mv_minmax(const float* x, long n, float* minmax, mv_stream_t stream) {
@@ -1369,11 +1296,10 @@ extern "C" int mv_minmax(const float* x, long n, float* minmax, mv_stream_t stre
   if (n == 0) return MV_OK;
   // minmax[2..3] (caller allocates 4 floats) hold the order-preserving integer image during the reduction
   unsigned* ord = reinterpret_cast<unsigned*>(minmax + 2);
-  minmax_begin_kernel<<<1, 1, 0, S_>>>(minmax, ord);
-  minmax_kernel<<<ew_grid(n), 256, 0, S_>>>(x, n, ord);
-  minmax_end_kernel<<<1, 1, 0, S_>>>(minmax, ord);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = mv_launch<minmax_begin_kernel>(MV_HERE, 1, 1, 0, s, minmax, ord)) return rc;
+  if (int rc = mv_launch<minmax_kernel>(MV_HERE, ew_grid(n), 256, 0, s, x, n, ord)) return rc;
+  return mv_launch<minmax_end_kernel>(MV_HERE, 1, 1, 0, s, minmax, ord);
 }
 
 extern "C" int mv_cross_entropy(const float* logits, const int64_t* labels, float* loss_sum, void* dlogits, int dl_dtype,
@@ -1385,49 +1311,35 @@ extern "C" int mv_cross_entropy(const float* logits, const int64_t* labels, floa
   // zeroed by a KERNEL, not hipMemsetAsync: captured into a HIP graph (utils/graph.py) the memset node of ROCm 7.2 did not
   // stay ordered in front of the kernels behind it from the second replay on (stat[2..3] garbage, the loss off or NaN while
   // every gradient stayed right: tools/diag/graph_ce_only.py)
-  mv_zero_f32_kernel<<<1, 64, 0, S_>>>(loss_sum, 4);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = mv_launch<mv_zero_f32_kernel>(MV_HERE, 1, 64, 0, s, loss_sum, 4)) return rc;
   const long total = outer * inner;
   if (total == 0) return MV_OK;
-  ce_label_scan_kernel<<<ew_grid(total), 256, 0, S_>>>(labels, total, C, loss_sum);
-  if (inner == 1) {
-    const int grid = ew_grid(total, 4);
-    if (dl_dtype == MV_BF16 && dlogits)
-      cross_entropy_kernel<bf16_t><<<grid, 256, 0, S_>>>(logits, labels, loss_sum, (bf16_t*)dlogits, ld_dl, argmax, outer,
-                                                         C, inner, grad_scale);
-    else
-      cross_entropy_kernel<float><<<grid, 256, 0, S_>>>(logits, labels, loss_sum, (float*)dlogits, ld_dl, argmax, outer, C,
-                                                        inner, grad_scale);
-  } else {
-    const int grid = ew_grid(total);
-    if (dl_dtype == MV_BF16 && dlogits)
-      cross_entropy_pixel_kernel<bf16_t><<<grid, 256, 0, S_>>>(logits, labels, loss_sum, (bf16_t*)dlogits, argmax, outer,
-                                                               C, inner, grad_scale);
-    else
-      cross_entropy_pixel_kernel<float><<<grid, 256, 0, S_>>>(logits, labels, loss_sum, (float*)dlogits, argmax, outer, C,
-                                                              inner, grad_scale);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  if (int rc = mv_launch<ce_label_scan_kernel>(MV_HERE, ew_grid(total), 256, 0, s, labels, total, C, loss_sum)) return rc;
+  return mv_pick<MV_F32, MV_BF16>(dlogits ? dl_dtype : MV_F32, [&](auto D) {       // without dlogits the dtype is not looked at
+    using T = mv_elem_t<D()>;
+    if (inner == 1)
+      return mv_launch<cross_entropy_kernel<T>>(MV_HERE, ew_grid(total, 4), 256, 0, s, logits, labels, loss_sum, (T*)dlogits, ld_dl, argmax,
+                                                outer, C, inner, grad_scale);
+    return mv_launch<cross_entropy_pixel_kernel<T>>(MV_HERE, ew_grid(total), 256, 0, s, logits, labels, loss_sum, (T*)dlogits, argmax, outer, C,
+                                                    inner, grad_scale);
+  });
 }
 
 extern "C" int mv_upsample_bilinear_fwd(const float* small, long sb, long sc, long sp, float* big, int B, int C, int h,
                                         int w, int H, int W, mv_stream_t stream) {
   MV_REQUIRE(B >= 0 && C > 0 && h > 0 && w > 0 && H > 0 && W > 0, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  upsample_fwd_kernel<<<ew_grid((long)B * C * H * W), 256, 0, S_>>>(small, sb, sc, sp, big, B, C, h, w, H, W,
-                                                                     (float)h / (float)H, (float)w / (float)W);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<upsample_fwd_kernel>(MV_HERE, ew_grid((long)B * C * H * W), 256, 0, (hipStream_t)stream, small, sb, sc, sp, big,
+                                        B, C, h, w, H, W, (float)h / (float)H, (float)w / (float)W);
 }
 
 extern "C" int mv_upsample_bilinear_bwd(const float* dbig, float* dsmall, long sb, long sc, long sp, int B, int C, int h,
                                         int w, int H, int W, mv_stream_t stream) {
   MV_REQUIRE(B >= 0 && C > 0 && h > 0 && w > 0 && H > 0 && W > 0, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  upsample_bwd_kernel<<<ew_grid((long)B * C * h * w), 256, 0, S_>>>(dbig, dsmall, sb, sc, sp, B, C, h, w, H, W,
-                                                                     (float)h / (float)H, (float)w / (float)W);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<upsample_bwd_kernel>(MV_HERE, ew_grid((long)B * C * h * w), 256, 0, (hipStream_t)stream, dbig, dsmall, sb, sc,
+                                        sp, B, C, h, w, H, W, (float)h / (float)H, (float)w / (float)W);
 }
 
 extern "C" int mv_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
@@ -1436,10 +1348,8 @@ extern "C" int mv_adamw(float* p, const float* g, float* m, float* v, long n, fl
   MV_REQUIRE(n >= 0, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
   MV_REQUIRE(mv_aligned16(p) && mv_aligned16(g) && mv_aligned16(m) && mv_aligned16(v), MV_ERR_ALIGN);
-  adamw_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_corr1,
-                                                     bias_corr2, grad_scale, clip_coef, nullptr);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<adamw_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
+                                 weight_decay, bias_corr1, bias_corr2, grad_scale, clip_coef, nullptr);
 }
 
 extern "C" int mv_adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2,
@@ -1447,19 +1357,16 @@ extern "C" int mv_adamw_dev(float* p, const float* g, float* m, float* v, long n
   MV_REQUIRE(n >= 0 && hyper != nullptr, MV_ERR_SHAPE);
   if (n == 0) return MV_OK;
   MV_REQUIRE(mv_aligned16(p) && mv_aligned16(g) && mv_aligned16(m) && mv_aligned16(v), MV_ERR_ALIGN);
-  adamw_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(p, g, m, v, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale,
-                                                     clip_coef, hyper);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<adamw_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2, eps,
+                                 weight_decay, 1.f, 1.f, grad_scale, clip_coef, hyper);
 }
 
 extern "C" int mv_sum_slabs(const float* slabs, long stride, int S, float* out, long n, int accumulate, mv_stream_t stream) {
   MV_REQUIRE(S >= 1 && n >= 0 && stride >= n && (stride & 3) == 0, MV_ERR_SHAPE);
   MV_REQUIRE(mv_aligned16(slabs) && mv_aligned16(out), MV_ERR_ALIGN);
   if (n == 0) return MV_OK;
-  sum_slabs_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(slabs, stride, S, accumulate ? out : nullptr, out, n);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<sum_slabs_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, slabs, stride, S,
+                                     accumulate ? out : nullptr, out, n);
 }
 
 extern "C" int mv_sum_slabs_add(const float* slabs, long stride, int S, const float* add, float* out, long n,
@@ -1467,9 +1374,7 @@ extern "C" int mv_sum_slabs_add(const float* slabs, long stride, int S, const fl
   MV_REQUIRE(S >= 1 && n >= 0 && stride >= n && (stride & 3) == 0, MV_ERR_SHAPE);
   MV_REQUIRE(mv_aligned16(slabs) && mv_aligned16(out) && mv_aligned16(add), MV_ERR_ALIGN);
   if (n == 0) return MV_OK;
-  sum_slabs_kernel<<<ew_grid((n + 3) / 4), 256, 0, S_>>>(slabs, stride, S, add, out, n);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<sum_slabs_kernel>(MV_HERE, ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream, slabs, stride, S, add, out, n);
 }
 
 extern "C" size_t mv_grad_norm_workspace_bytes(void) { return GN_PARTS * sizeof(double); }
@@ -1479,10 +1384,8 @@ extern "C" int mv_grad_norm_clip(const float* g, long n, float grad_scale, float
   MV_REQUIRE(n >= 0 && max_norm >= 0.f, MV_ERR_SHAPE);
   MV_REQUIRE(mv_aligned16(g) && mv_aligned16(workspace), MV_ERR_ALIGN);
   MV_REQUIRE(workspace_bytes >= mv_grad_norm_workspace_bytes(), MV_ERR_WORKSPACE);
-  sumsq_partial_kernel<<<GN_PARTS, 256, 0, S_>>>(g, n, (double*)workspace);
-  grad_norm_finish_kernel<<<1, 256, 0, S_>>>((const double*)workspace, grad_scale, max_norm, out);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  if (int rc = mv_launch<sumsq_partial_kernel>(MV_HERE, GN_PARTS, 256, 0, (hipStream_t)stream, g, n, (double*)workspace)) return rc;
+  return mv_launch<grad_norm_finish_kernel>(MV_HERE, 1, 256, 0, (hipStream_t)stream, (const double*)workspace, grad_scale, max_norm, out);
 }
 
 extern "C" int mv_dropout(const void* x, void* y, int dtype, long n, float p, uint64_t seed, uint64_t offset,
@@ -1493,10 +1396,8 @@ extern "C" int mv_dropout(const void* x, void* y, int dtype, long n, float p, ui
   const unsigned thr = (unsigned)((double)p * 4294967296.0);       // keep  <=>  random u32 >= thr
   const float scale = 1.0f / (1.0f - p);
   const int grid = ew_grid((n + 3) / 4);
-  if (dtype == MV_F32)
-    dropout_kernel<float><<<grid, 256, 0, S_>>>((const float*)x, (float*)y, n, thr, scale, seed, offset);
-  else
-    dropout_kernel<bf16_t><<<grid, 256, 0, S_>>>((const bf16_t*)x, (bf16_t*)y, n, thr, scale, seed, offset);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(dtype, [&](auto D) {
+    using T = mv_elem_t<D()>;
+    return mv_launch<dropout_kernel<T>>(MV_HERE, grid, 256, 0, (hipStream_t)stream, (const T*)x, (T*)y, n, thr, scale, seed, offset);
+  });
 }

@@ -1994,9 +1994,7 @@ int tn_splitk(const TnPlan& pl, float* C, int ldc, int M, int N, int accumulate,
   if (rc != MV_OK || direct) return rc;
   int grid = mv_cdiv(slab_stride, 256);
   if (grid > 2048) grid = 2048;
-  splitk_reduce_kernel<<<grid, 256, 0, s>>>(workspace, slab_stride, pl.splits, C, ldc, M, N, accumulate);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<splitk_reduce_kernel>(MV_HERE, grid, 256, 0, s, workspace, slab_stride, pl.splits, C, ldc, M, N, accumulate);
 }
 
 // NSEG = 6: the bf16x6 pairings over three pieces per operand; NSEG = 3: the bf16x3 pairings (0,0) (0,1) (1,0) over TWO pieces per
@@ -2158,21 +2156,18 @@ extern "C" int mv_colsum(const void* x, int x_dtype, long ld, float* out, int ac
   MV_REQUIRE(workspace_bytes >= (size_t)parts * cols * sizeof(float), MV_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
   if (x_dtype == MV_F32 && rows <= 2048) {      // already a partial-sum table (e.g. the DGELU epilogue's): one stage is enough
-    mv_reduce_rows_kernel<<<mv_reduce_rows_grid(cols), 1024, 0, s>>>((const float*)x, (int)rows, cols, ld, out, out, out, cols, cols,
-                                                                     accumulate);
-    MV_CHECK_LAUNCH();
-    return MV_OK;
+    return mv_launch<mv_reduce_rows_kernel>(MV_HERE, mv_reduce_rows_grid(cols), 1024, 0, s, (const float*)x, (int)rows, cols, ld,
+                                            out, out, out, cols, cols, accumulate);
   }
   const int rpb = (int)((rows + parts - 1) / parts);
   dim3 grid(mv_cdiv(cols, 256), parts);
-  if (x_dtype == MV_F32)
-    colsum_partial_kernel<float><<<grid, 256, 0, s>>>((const float*)x, ld, workspace, rows, cols, rpb < 1 ? 1 : rpb);
-  else
-    colsum_partial_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, ld, workspace, rows, cols, rpb < 1 ? 1 : rpb);
-  MV_CHECK_LAUNCH();
-  mv_reduce_rows_kernel<<<mv_reduce_rows_grid(cols), 1024, 0, s>>>(workspace, parts, cols, (long)cols, out, out, out, cols, cols, accumulate);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const int rc = mv_pick<MV_F32, MV_BF16>(x_dtype, [&](auto D) {
+    using T = mv_elem_t<D()>;
+    return mv_launch<colsum_partial_kernel<T>>(MV_HERE, grid, 256, 0, s, (const T*)x, ld, workspace, rows, cols, rpb < 1 ? 1 : rpb);
+  });
+  if (rc != MV_OK) return rc;
+  return mv_launch<mv_reduce_rows_kernel>(MV_HERE, mv_reduce_rows_grid(cols), 1024, 0, s, workspace, parts, cols, (long)cols, out,
+                                          out, out, cols, cols, accumulate);
 }
 
 extern "C" int mv_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int Kc,

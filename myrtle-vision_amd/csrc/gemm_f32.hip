@@ -501,87 +501,36 @@ extern "C" int mv_gemm_f32(const float* A, long sa_m, long sa_k, long sa_b1, lon
   MV_REQUIRE(M >= 0 && N >= 0 && K >= 0 && nb1 >= 1 && nb2 >= 1, MV_ERR_SHAPE);
   if (M == 0 || N == 0) return MV_OK;
   MV_REQUIRE((long)nb1 * nb2 <= 65535, MV_ERR_SHAPE);
+  MV_REQUIRE(aux || epilogue == MV_EPI_NONE || epilogue == MV_EPI_GELU, MV_ERR_UNSUPPORTED);
+  MV_REQUIRE(aux_i > 0 || epilogue != MV_EPI_EMBED, MV_ERR_UNSUPPORTED);
   F32Args a{A, sa_m, sa_k, sa_b1, sa_b2, B, sb_k, sb_n, sb_b1, sb_b2, C, sc_m, sc_n, sc_b1, sc_b2,
             M, N, K, nb2, alpha, accumulate, bias, aux, ld_aux, aux_i, out2, ld_out2};
   hipStream_t s = (hipStream_t)stream;
   // Matrix-core form (bit-identical results).  128 x 128 blocks when that wastes little of the last row / column of blocks,
   // 64 x 64 otherwise (M = N = 197: 77 % useful instead of 59 %).  mv_gemm_f32_force_fma(1) / MV_GEMM_F32=fma keeps the FMA kernel.
-  if (!g_f32_fma.load(std::memory_order_relaxed)) {
-    const long pad128 = (long)mv_cdiv(M, 128) * 128 * mv_cdiv(N, 128) * 128, pad64 = (long)mv_cdiv(M, 64) * 64 * mv_cdiv(N, 64) * 64;
-    const bool big = pad128 * 10 <= pad64 * 11;             // at most 10 % more padded work than the 64-tiles need
-    // fast form: K % 16 == 0, one unit stride per operand, everything 16-byte addressable
-    const bool ak = sa_k == 1, am = sa_m == 1, bk = sb_k == 1, bn = sb_n == 1;
-    auto al4 = [](long v) { return (v & 3) == 0; };
-    const bool fast = big && K >= 16 && K % 16 == 0 && M >= 4 && N >= 4 && (ak || am) && (bk || bn) && mv_aligned16(A) &&
-                      mv_aligned16(B) && al4(sa_b1) && al4(sa_b2) && al4(sb_b1) && al4(sb_b2) &&
-                      (ak ? al4(sa_m) : (al4(sa_k) && M % 4 == 0)) && (bk ? al4(sb_n) : (al4(sb_k) && N % 4 == 0)) &&
-                      !g_f32_generic.load(std::memory_order_relaxed);
-    if (fast) {
-      const dim3 fgrid(mv_cdiv(N, 128), mv_cdiv(M, 128), nb1 * nb2);
-#define MV_F32_FAST(E)                                                                     \
-      if (ak && bk) gemm_f32_mfma_fast_kernel<E, true, true><<<fgrid, 256, 0, s>>>(a);     \
-      else if (ak) gemm_f32_mfma_fast_kernel<E, true, false><<<fgrid, 256, 0, s>>>(a);     \
-      else if (bk) gemm_f32_mfma_fast_kernel<E, false, true><<<fgrid, 256, 0, s>>>(a);     \
-      else gemm_f32_mfma_fast_kernel<E, false, false><<<fgrid, 256, 0, s>>>(a);
-      switch (epilogue) {
-        case MV_EPI_NONE: MV_F32_FAST(MV_EPI_NONE) break;
-        case MV_EPI_GELU: MV_F32_FAST(MV_EPI_GELU) break;
-        case MV_EPI_RESIDUAL:
-          MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-          MV_F32_FAST(MV_EPI_RESIDUAL) break;
-        case MV_EPI_DGELU:
-          MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-          MV_F32_FAST(MV_EPI_DGELU) break;
-        case MV_EPI_EMBED:
-          MV_REQUIRE(aux && aux_i > 0, MV_ERR_UNSUPPORTED);
-          MV_F32_FAST(MV_EPI_EMBED) break;
-        default: return MV_ERR_UNSUPPORTED;
-      }
-#undef MV_F32_FAST
-      MV_CHECK_LAUNCH();
-      return MV_OK;
-    }
-#define MV_F32_LAUNCH(E)                                                                                    \
-    if (big) gemm_f32_mfma_kernel<E, 4><<<dim3(mv_cdiv(N, 128), mv_cdiv(M, 128), nb1 * nb2), 256, 0, s>>>(a); \
-    else gemm_f32_mfma_kernel<E, 2><<<dim3(mv_cdiv(N, 64), mv_cdiv(M, 64), nb1 * nb2), 256, 0, s>>>(a);
-    switch (epilogue) {
-      case MV_EPI_NONE: MV_F32_LAUNCH(MV_EPI_NONE) break;
-      case MV_EPI_GELU: MV_F32_LAUNCH(MV_EPI_GELU) break;
-      case MV_EPI_RESIDUAL:
-        MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-        MV_F32_LAUNCH(MV_EPI_RESIDUAL) break;
-      case MV_EPI_DGELU:
-        MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-        MV_F32_LAUNCH(MV_EPI_DGELU) break;
-      case MV_EPI_EMBED:
-        MV_REQUIRE(aux && aux_i > 0, MV_ERR_UNSUPPORTED);
-        MV_F32_LAUNCH(MV_EPI_EMBED) break;
-      default: return MV_ERR_UNSUPPORTED;
-    }
-#undef MV_F32_LAUNCH
-    MV_CHECK_LAUNCH();
-    return MV_OK;
-  }
-  dim3 grid(mv_cdiv(N, TN), mv_cdiv(M, TM), nb1 * nb2);
-  switch (epilogue) {
-    case MV_EPI_NONE: gemm_f32_kernel<MV_EPI_NONE><<<grid, 256, 0, s>>>(a); break;
-    case MV_EPI_GELU: gemm_f32_kernel<MV_EPI_GELU><<<grid, 256, 0, s>>>(a); break;
-    case MV_EPI_RESIDUAL:
-      MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-      gemm_f32_kernel<MV_EPI_RESIDUAL><<<grid, 256, 0, s>>>(a);
-      break;
-    case MV_EPI_DGELU:
-      MV_REQUIRE(aux, MV_ERR_UNSUPPORTED);
-      gemm_f32_kernel<MV_EPI_DGELU><<<grid, 256, 0, s>>>(a);
-      break;
-    case MV_EPI_EMBED:
-      MV_REQUIRE(aux && aux_i > 0, MV_ERR_UNSUPPORTED);
-      gemm_f32_kernel<MV_EPI_EMBED><<<grid, 256, 0, s>>>(a);
-      break;
-    default: return MV_ERR_UNSUPPORTED;
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const bool mfma = !g_f32_fma.load(std::memory_order_relaxed);
+  const long pad128 = (long)mv_cdiv(M, 128) * 128 * mv_cdiv(N, 128) * 128, pad64 = (long)mv_cdiv(M, 64) * 64 * mv_cdiv(N, 64) * 64;
+  const bool big = pad128 * 10 <= pad64 * 11;             // at most 10 % more padded work than the 64-tiles need
+  // fast form: K % 16 == 0, one unit stride per operand, everything 16-byte addressable
+  const bool ak = sa_k == 1, am = sa_m == 1, bk = sb_k == 1, bn = sb_n == 1;
+  auto al4 = [](long v) { return (v & 3) == 0; };
+  const bool fast = big && K >= 16 && K % 16 == 0 && M >= 4 && N >= 4 && (ak || am) && (bk || bn) && mv_aligned16(A) &&
+                    mv_aligned16(B) && al4(sa_b1) && al4(sa_b2) && al4(sb_b1) && al4(sb_b2) &&
+                    (ak ? al4(sa_m) : (al4(sa_k) && M % 4 == 0)) && (bk ? al4(sb_n) : (al4(sb_k) && N % 4 == 0)) &&
+                    !g_f32_generic.load(std::memory_order_relaxed);
+  const int nb = nb1 * nb2;
+  return mv_pick<MV_EPI_NONE, MV_EPI_GELU, MV_EPI_RESIDUAL, MV_EPI_DGELU, MV_EPI_EMBED>(epilogue, [&](auto EPI) {
+    constexpr int E = decltype(EPI)::value;
+    if (!mfma) return mv_launch<gemm_f32_kernel<E>>(MV_HERE, dim3(mv_cdiv(N, TN), mv_cdiv(M, TM), nb), 256, 0, s, a);
+    if (!big) return mv_launch<gemm_f32_mfma_kernel<E, 2>>(MV_HERE, dim3(mv_cdiv(N, 64), mv_cdiv(M, 64), nb), 256, 0, s, a);
+    const dim3 grid(mv_cdiv(N, 128), mv_cdiv(M, 128), nb);
+    if (!fast) return mv_launch<gemm_f32_mfma_kernel<E, 4>>(MV_HERE, grid, 256, 0, s, a);
+    return mv_pick<0, 1>(ak, [&](auto AK) {
+      return mv_pick<0, 1>(bk, [&](auto BK) {
+        return mv_launch<gemm_f32_mfma_fast_kernel<E, (bool)decltype(AK)::value, (bool)decltype(BK)::value>>(MV_HERE, grid, 256, 0, s, a);
+      });
+    });
+  });
 }
 
 extern "C" int mv_softmax_fwd(const float* x, float* y, long rows, int cols, float scale, mv_stream_t stream) {
@@ -589,9 +538,7 @@ extern "C" int mv_softmax_fwd(const float* x, float* y, long rows, int cols, flo
   if (rows == 0) return MV_OK;
   long g = (rows + 3) / 4;
   if (g > 4096) g = 4096;
-  softmax_fwd_kernel<<<(int)g, 256, 0, (hipStream_t)stream>>>(x, y, rows, cols, scale);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<softmax_fwd_kernel>(MV_HERE, (int)g, 256, 0, (hipStream_t)stream, x, y, rows, cols, scale);
 }
 
 extern "C" int mv_softmax_bwd(const float* y, const float* dy, float* dx, long rows, int cols, float scale,
@@ -600,7 +547,5 @@ extern "C" int mv_softmax_bwd(const float* y, const float* dy, float* dx, long r
   if (rows == 0) return MV_OK;
   long g = (rows + 3) / 4;
   if (g > 4096) g = 4096;
-  softmax_bwd_kernel<<<(int)g, 256, 0, (hipStream_t)stream>>>(y, dy, dx, rows, cols, scale);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<softmax_bwd_kernel>(MV_HERE, (int)g, 256, 0, (hipStream_t)stream, y, dy, dx, rows, cols, scale);
 }

@@ -153,8 +153,6 @@ __global__ __launch_bounds__(256) void image_prepare_ragged_kernel(const uint8_t
 
 }  // namespace
 
-#define S_ ((hipStream_t)stream)
-
 extern "C" int mv_image_prepare(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* kh, const int32_t* bh,
                                 const int32_t* kv, const int32_t* bv, int ks, const uint8_t* flip, float mean0, float mean1,
                                 float mean2, float std0, float std1, float std2, float* out, int B, int out_h, int out_w,
@@ -162,10 +160,9 @@ extern "C" int mv_image_prepare(const uint8_t* src, long img_stride, int Hs, int
   MV_REQUIRE(B >= 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0 && ks > 0 && ks <= 64, MV_ERR_SHAPE);
   MV_REQUIRE(img_stride >= (long)Hs * Ws * 3 && B <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  image_prepare_kernel<false><<<dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, S_>>>(
-      src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, flip, mean0, mean1, mean2, std0, std1, std2, out, nullptr, out_h, out_w);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<image_prepare_kernel<false>>(MV_HERE, dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0,
+                                                (hipStream_t)stream, src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, flip, mean0,
+                                                mean1, mean2, std0, std1, std2, out, nullptr, out_h, out_w);
 }
 
 extern "C" int mv_mask_prepare(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* yi, const int32_t* xi,
@@ -173,10 +170,8 @@ extern "C" int mv_mask_prepare(const uint8_t* src, long img_stride, int Hs, int 
   MV_REQUIRE(B >= 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0, MV_ERR_SHAPE);
   MV_REQUIRE(img_stride >= (long)Hs * Ws && B <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  mask_prepare_kernel<false><<<dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, S_>>>(src, img_stride, Ws, yi, xi, flip, add,
-                                                                                            out, nullptr, out_h, out_w);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<mask_prepare_kernel<false>>(MV_HERE, dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, (hipStream_t)stream,
+                                               src, img_stride, Ws, yi, xi, flip, add, out, nullptr, out_h, out_w);
 }
 
 extern "C" int mv_image_resize_u8(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* kh, const int32_t* bh,
@@ -185,10 +180,9 @@ extern "C" int mv_image_resize_u8(const uint8_t* src, long img_stride, int Hs, i
   MV_REQUIRE(B >= 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0 && ks > 0 && ks <= 64, MV_ERR_SHAPE);
   MV_REQUIRE(img_stride >= (long)Hs * Ws * 3 && B <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  image_prepare_kernel<true><<<dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, S_>>>(
-      src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, nullptr, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, nullptr, out, out_h, out_w);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<image_prepare_kernel<true>>(MV_HERE, dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, (hipStream_t)stream,
+                                               src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, nullptr, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f,
+                                               nullptr, out, out_h, out_w);
 }
 
 extern "C" int mv_mask_resize_u8(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* yi, const int32_t* xi,
@@ -196,10 +190,8 @@ extern "C" int mv_mask_resize_u8(const uint8_t* src, long img_stride, int Hs, in
   MV_REQUIRE(B >= 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0, MV_ERR_SHAPE);
   MV_REQUIRE(img_stride >= (long)Hs * Ws && B <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  mask_prepare_kernel<true><<<dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, S_>>>(src, img_stride, Ws, yi, xi, nullptr, 0,
-                                                                                           nullptr, out, out_h, out_w);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<mask_prepare_kernel<true>>(MV_HERE, dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, (hipStream_t)stream,
+                                              src, img_stride, Ws, yi, xi, nullptr, 0, nullptr, out, out_h, out_w);
 }
 
 extern "C" int mv_image_prepare_ragged(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* kh, const int32_t* bh,
@@ -209,10 +201,9 @@ extern "C" int mv_image_prepare_ragged(const uint8_t* src, long img_stride, int 
   MV_REQUIRE(B >= 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0 && ks > 0 && ks <= 64, MV_ERR_SHAPE);
   MV_REQUIRE(img_stride >= (long)Hs * Ws * 3 && B <= 65535 && mv_cdiv(out_h, 4) <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  image_prepare_ragged_kernel<false><<<dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, S_>>>(
-      src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, ext, mean0, mean1, mean2, std0, std1, std2, out, pad_mask, nullptr, out_h, out_w);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<image_prepare_ragged_kernel<false>>(MV_HERE, dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0,
+                                                       (hipStream_t)stream, src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, ext, mean0,
+                                                       mean1, mean2, std0, std1, std2, out, pad_mask, nullptr, out_h, out_w);
 }
 
 extern "C" int mv_image_resize_u8_ragged(const uint8_t* src, long img_stride, int Hs, int Ws, const int32_t* kh, const int32_t* bh,
@@ -221,8 +212,7 @@ extern "C" int mv_image_resize_u8_ragged(const uint8_t* src, long img_stride, in
   MV_REQUIRE(B >= 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0 && ks > 0 && ks <= 64, MV_ERR_SHAPE);
   MV_REQUIRE(img_stride >= (long)Hs * Ws * 3 && B <= 65535 && mv_cdiv(out_h, 4) <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  image_prepare_ragged_kernel<true><<<dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0, S_>>>(
-      src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, ext, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, nullptr, nullptr, out, out_h, out_w);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<image_prepare_ragged_kernel<true>>(MV_HERE, dim3(mv_cdiv(out_w, 64), mv_cdiv(out_h, 4), B), 256, 0,
+                                                      (hipStream_t)stream, src, img_stride, Hs, Ws, kh, bh, kv, bv, ks, ext, 0.f,
+                                                      0.f, 0.f, 1.f, 1.f, 1.f, nullptr, nullptr, out, out_h, out_w);
 }

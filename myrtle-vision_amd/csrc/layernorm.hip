@@ -230,20 +230,12 @@ extern "C" size_t mv_layernorm_bwd_workspace_bytes(int rows, int dim) {
   return (size_t)ln_grid(rows) * 3 * (size_t)dim * sizeof(float);
 }
 
-// launch with the grid capped at the workgroups resident at once (MV_RESIDENT_BLOCKS: the wide and the split-output forms keep
-// fewer than the eight groups per CU that the 2 048 cap assumes)
-#define LN_GO(args_, ...)                                                        \
-  do {                                                                           \
-    const int g_ = min(grid, MV_RESIDENT_BLOCKS((__VA_ARGS__), 256, 0));         \
-    __VA_ARGS__<<<g_, 256, 0, s>>> args_;                                        \
-  } while (0)
-#define LN_FWD_CASE(V)                                                                                      \
-  case V:                                                                                                   \
-    if (y_dtype == MV_F32)                                                                                  \
-      LN_GO((x, ldx, gamma, beta, (float*)y, mean, rstd, rows, dim, eps), ln_fwd_kernel<V, float>); \
-    else                                                                                                    \
-      LN_GO((x, ldx, gamma, beta, (bf16_t*)y, mean, rstd, rows, dim, eps), ln_fwd_kernel<V, bf16_t>); \
-    break;
+// launch of ln_fwd_kernel<..> with the grid capped at the workgroups resident at once (mv_resident_blocks: the wide and the
+// split-output forms keep fewer than the eight groups per CU that the 2 048 cap assumes)
+template <auto K, typename... A>
+static int ln_go(mv_site at, int grid, hipStream_t s, A... args) {
+  return mv_launch<K>(at, min(grid, mv_resident_blocks<K>(256, 0)), 256, 0, s, args...);
+}
 
 extern "C" int mv_layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, void* y, int y_dtype,
                                 float* mean, float* rstd, int rows, int dim, float eps, mv_stream_t stream) {
@@ -255,22 +247,13 @@ extern "C" int mv_layernorm_fwd(const float* x, long ldx, const float* gamma, co
   int grid = mv_cdiv(rows, 4);
   if (grid > 2048) grid = 2048;  // grid-stride beyond 8 blocks per CU
   const int vpl = mv_cdiv(dim / 4, 64);
-  switch (vpl) {
-    LN_FWD_CASE(1) LN_FWD_CASE(2) LN_FWD_CASE(3) LN_FWD_CASE(4)
-    case 5: case 6: case 7: case 8:
-      if (y_dtype == MV_F32)
-        LN_GO((x, ldx, gamma, beta, (float*)y, mean, rstd, rows, dim, eps), ln_fwd_kernel<8, float>);
-      else
-        LN_GO((x, ldx, gamma, beta, (bf16_t*)y, mean, rstd, rows, dim, eps), ln_fwd_kernel<8, bf16_t>);
-      break;
-    default:
-      if (y_dtype == MV_F32)
-        LN_GO((x, ldx, gamma, beta, (float*)y, mean, rstd, rows, dim, eps), ln_fwd_kernel<16, float>);
-      else
-        LN_GO((x, ldx, gamma, beta, (bf16_t*)y, mean, rstd, rows, dim, eps), ln_fwd_kernel<16, bf16_t>);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<1, 2, 3, 4, 8, 16>(vpl <= 4 ? vpl : vpl <= 8 ? 8 : 16, [&](auto V) {
+    return mv_pick<MV_F32, MV_BF16>(y_dtype, [&](auto D) {
+      using T = mv_elem_t<decltype(D)::value>;
+      return ln_go<ln_fwd_kernel<decltype(V)::value, T>>(MV_HERE, grid, s, x, ldx, gamma, beta, (T*)y, mean, rstd, rows, dim, eps,
+                                                          0.f, 0.f);
+    });
+  });
 }
 
 extern "C" int mv_layernorm_fwd_split(const float* x, long ldx, const float* gamma, const float* beta, void* y_split, int nseg,
@@ -283,20 +266,12 @@ extern "C" int mv_layernorm_fwd_split(const float* x, long ldx, const float* gam
   int grid = mv_cdiv(rows, 4);
   if (grid > 2048) grid = 2048;
   bf16_t* y = (bf16_t*)y_split;
-#define LN_SPLIT_CASE(V)                                                                                               \
-  case V:                                                                                                              \
-    if (nseg == 3) LN_GO((x, ldx, gamma, beta, y, mean, rstd, rows, dim, eps), ln_fwd_kernel<V, bf16_t, 3>); \
-    else LN_GO((x, ldx, gamma, beta, y, mean, rstd, rows, dim, eps), ln_fwd_kernel<V, bf16_t, 6>);           \
-    break;
-  switch (mv_cdiv(dim / 4, 64)) {
-    LN_SPLIT_CASE(1) LN_SPLIT_CASE(2) LN_SPLIT_CASE(3)
-    default:
-      if (nseg == 3) LN_GO((x, ldx, gamma, beta, y, mean, rstd, rows, dim, eps), ln_fwd_kernel<4, bf16_t, 3>);
-      else LN_GO((x, ldx, gamma, beta, y, mean, rstd, rows, dim, eps), ln_fwd_kernel<4, bf16_t, 6>);
-  }
-#undef LN_SPLIT_CASE
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<1, 2, 3, 4>(min(mv_cdiv(dim / 4, 64), 4), [&](auto V) {
+    return mv_pick<3, 6>(nseg, [&](auto NSEG) {
+      return ln_go<ln_fwd_kernel<decltype(V)::value, bf16_t, decltype(NSEG)::value>>(MV_HERE, grid, s, x, ldx, gamma, beta, y, mean, rstd, rows,
+                                                                                     dim, eps, 0.f, 0.f);
+    });
+  });
 }
 
 extern "C" int mv_layernorm_fwd_q8(const float* x, long ldx, const float* gamma, const float* beta, void* codes, int rows,
@@ -309,29 +284,14 @@ extern "C" int mv_layernorm_fwd_q8(const float* x, long ldx, const float* gamma,
   int grid = mv_cdiv(rows, 4);
   if (grid > 2048) grid = 2048;
   const float inv = 1.0f / scale, fz = (float)zero_point;
-  switch (mv_cdiv(dim / 4, 64)) {
-    case 1: ln_fwd_kernel<1, int8_t><<<grid, 256, 0, s>>>(x, ldx, gamma, beta, (int8_t*)codes, nullptr, nullptr, rows, dim, eps, inv, fz); break;
-    case 2: ln_fwd_kernel<2, int8_t><<<grid, 256, 0, s>>>(x, ldx, gamma, beta, (int8_t*)codes, nullptr, nullptr, rows, dim, eps, inv, fz); break;
-    case 3: ln_fwd_kernel<3, int8_t><<<grid, 256, 0, s>>>(x, ldx, gamma, beta, (int8_t*)codes, nullptr, nullptr, rows, dim, eps, inv, fz); break;
-    default: ln_fwd_kernel<4, int8_t><<<grid, 256, 0, s>>>(x, ldx, gamma, beta, (int8_t*)codes, nullptr, nullptr, rows, dim, eps, inv, fz); break;
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<1, 2, 3, 4>(min(mv_cdiv(dim / 4, 64), 4), [&](auto V) {
+    return mv_launch<ln_fwd_kernel<V(), int8_t>>(MV_HERE, grid, 256, 0, s, x, ldx, gamma, beta, (int8_t*)codes, nullptr, nullptr, rows, dim,
+                                                 eps, inv, fz);
+  });
 }
 
 // grid: every workgroup resident at once (the kernel keeps 142 registers at dim 768: three groups per CU, not the four that
 // ln_grid's 1 024 assumes)
-#define LN_BWD_LAUNCH(V)                                                                                     \
-  if (dy_dtype == MV_F32) {                                                                                  \
-    grid = min(grid, MV_RESIDENT_BLOCKS((ln_bwd_kernel<V, float>), 256, 0));                                 \
-    ln_bwd_kernel<V, float><<<grid, 256, 0, s>>>((const float*)dy, x, ldx, gamma, mean, rstd, dx_add, dx, lddx, \
-                                                 workspace, rows, dim, (bf16_t*)dx_bf16, dx_colsum != nullptr, nseg); \
-  } else {                                                                                                   \
-    grid = min(grid, MV_RESIDENT_BLOCKS((ln_bwd_kernel<V, bf16_t>), 256, 0));                                \
-    ln_bwd_kernel<V, bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)dy, x, ldx, gamma, mean, rstd, dx_add, dx, lddx, \
-                                                  workspace, rows, dim, (bf16_t*)dx_bf16, dx_colsum != nullptr, nseg); \
-  }
-
 namespace {
 int ln_bwd_impl(const void* dy, int dy_dtype, const float* x, long ldx, const float* gamma, const float* mean, const float* rstd,
                 const float* dx_add, float* dx, long lddx, float* dgamma, float* dbeta, int accumulate, float* workspace,
@@ -365,32 +325,31 @@ int ln_bwd_impl(const void* dy, int dy_dtype, const float* x, long ldx, const fl
   hipStream_t s = (hipStream_t)stream;
   int grid = ln_grid(rows);
   if (rows > 0) {
-    const int vpl = mv_cdiv(dim / 4, 64);
-    switch (vpl) {
-      case 1: LN_BWD_LAUNCH(1) break;
-      case 2: LN_BWD_LAUNCH(2) break;
-      case 3: LN_BWD_LAUNCH(3) break;
-      case 4: LN_BWD_LAUNCH(4) break;
-      default: LN_BWD_LAUNCH(8) break;
-    }
-    MV_CHECK_LAUNCH();
+    // grid: every workgroup resident at once (the kernel keeps 142 registers at dim 768: three groups per CU, not the four that
+    // ln_grid's 1 024 assumes)
+    const int rc = mv_pick<1, 2, 3, 4, 8>(mv_cdiv(dim / 4, 64) <= 4 ? mv_cdiv(dim / 4, 64) : 8, [&](auto V) {
+      return mv_pick<MV_F32, MV_BF16>(dy_dtype, [&](auto D) {
+        using T = mv_elem_t<decltype(D)::value>;
+        constexpr auto K = ln_bwd_kernel<decltype(V)::value, T>;
+        grid = min(grid, mv_resident_blocks<K>(256, 0));
+        return mv_launch<K>(MV_HERE, grid, 256, 0, s, (const T*)dy, x, ldx, gamma, mean, rstd, dx_add, dx, lddx, workspace, rows, dim,
+                            (bf16_t*)dx_bf16, dx_colsum != nullptr, nseg);
+      });
+    });
+    if (rc != MV_OK) return rc;
   }
   const int groups = dx_colsum ? 3 : 2;
   // ONE finishing launch for all (2 or 3) column groups of the workspace: dgamma | dbeta | dx column sums.  (accumulate
   // applies to dgamma/dbeta; the column sums are always overwritten: their group is reduced into a zero-initialised
   // view only when accumulate == 0, otherwise it takes its own launch.)
-  if (dx_colsum && accumulate) {
-    mv_reduce_rows_kernel<<<mv_reduce_rows_grid(2 * dim), 1024, 0, s>>>(workspace, rows > 0 ? grid : 0, 2 * dim, (long)groups * dim,
-                                                                        dgamma, dbeta, dbeta, dim, 2 * dim, 1);
-    MV_CHECK_LAUNCH();
-    mv_reduce_rows_kernel<<<mv_reduce_rows_grid(dim), 1024, 0, s>>>(workspace + 2 * dim, rows > 0 ? grid : 0, dim,
-                                                                    (long)groups * dim, dx_colsum, dx_colsum, dx_colsum, dim, dim, 0);
-  } else {
-    mv_reduce_rows_kernel<<<mv_reduce_rows_grid(groups * dim), 1024, 0, s>>>(workspace, rows > 0 ? grid : 0, groups * dim,
-                                                                             (long)groups * dim, dgamma, dbeta, dx_colsum, dim,
-                                                                             2 * dim, accumulate);
-  }
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  const int nparts = rows > 0 ? grid : 0;
+  if (!(dx_colsum && accumulate))
+    return mv_launch<mv_reduce_rows_kernel>(MV_HERE, mv_reduce_rows_grid(groups * dim), 1024, 0, s, workspace, nparts, groups * dim,
+                                            (long)groups * dim, dgamma, dbeta, dx_colsum, dim, 2 * dim, accumulate);
+  if (int rc = mv_launch<mv_reduce_rows_kernel>(MV_HERE, mv_reduce_rows_grid(2 * dim), 1024, 0, s, workspace, nparts, 2 * dim,
+                                                (long)groups * dim, dgamma, dbeta, dbeta, dim, 2 * dim, 1))
+    return rc;
+  return mv_launch<mv_reduce_rows_kernel>(MV_HERE, mv_reduce_rows_grid(dim), 1024, 0, s, workspace + 2 * dim, nparts, dim,
+                                          (long)groups * dim, dx_colsum, dx_colsum, dx_colsum, dim, dim, 0);
 }
 }  // namespace

@@ -9,6 +9,8 @@
 
 #include <atomic>
 #include <mutex>
+#include <tuple>
+#include <type_traits>
 
 // Compute units of the CURRENT device (persistent-kernel grid sizes), remembered per device like the LDS grants of mv_launch below.
 inline int mv_cu_count() {
@@ -24,26 +26,6 @@ inline int mv_cu_count() {
   if (have) n_[d].store(n, std::memory_order_release);
   return n;
 }
-
-// Workgroups of `kernel_` (threads_ per group, dyn_lds_ bytes of dynamic LDS) that are RESIDENT on the current device at once:
-// the grid of a grid-stride kernel whose register count limits occupancy.  A larger grid runs in rounds, and the last round
-// leaves most of the chip idle (LayerNorm backward: 1 024 groups against 768 resident ran 1.33 rounds, -22 %).
-#define MV_RESIDENT_BLOCKS(kernel_, threads_, dyn_lds_)                                                        \
-  ([&]() -> int {                                                                                              \
-    static std::atomic<int> n_[32] = {};                                                                       \
-    int d_ = 0;                                                                                                \
-    const bool have_ = hipGetDevice(&d_) == hipSuccess && d_ >= 0 && d_ < 32;                                  \
-    if (have_) {                                                                                               \
-      const int c_ = n_[d_].load(std::memory_order_acquire);                                                   \
-      if (c_ > 0) return c_;                                                                                   \
-    }                                                                                                          \
-    int per_cu_ = 0;                                                                                           \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_, kernel_, threads_, dyn_lds_) != hipSuccess || per_cu_ <= 0) \
-      per_cu_ = 1;                                                                                             \
-    const int r_ = per_cu_ * mv_cu_count();                                                                    \
-    if (have_) n_[d_].store(r_, std::memory_order_release);                                                    \
-    return r_;                                                                                                 \
-  }())
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -73,10 +55,6 @@ inline int mv_check_launch(mv_site at) {
     fprintf(stderr, "[myrtle_vision_hip] %s:%d: HIP error %d (%s)\n", at.file, at.line, (int)e, hipGetErrorString(e));
   return MV_ERR_LAUNCH;
 }
-#define MV_CHECK_LAUNCH()                                           \
-  do {                                                              \
-    if (mv_check_launch(MV_HERE) != MV_OK) return MV_ERR_LAUNCH;    \
-  } while (0)
 
 // Whether kernel K may be launched with `lds` bytes of dynamic LDS on the current device, raising its limit if it has to.
 // hipFuncSetAttribute acts on ONE kernel instantiation and on the CURRENT device, and a kernel starts at the default 64 KiB.  So
@@ -99,7 +77,8 @@ inline bool mv_grant_lds(size_t lds) {
   return true;
 }
 
-// THE way to launch a kernel with dynamic LDS: mv_launch<kernel<ARGS>>(MV_HERE, grid, block, lds, stream, kernel arguments...).
+// THE way to launch a kernel: mv_launch<kernel<ARGS>>(MV_HERE, grid, block, lds, stream, kernel arguments...).  Every launch is
+// checked where it is made, so a sequence of launches is `if (int rc = mv_launch<..>(..)) return rc;` and stops at the first failure.
 // The kernel and the byte count are named once; the grant above and the launch cannot be paired wrongly.  MV_OK or MV_ERR_LAUNCH
 // (a failed raise does not launch).  lds == 0 adds nothing to the launch and its check.
 template <auto K, typename... A>
@@ -109,8 +88,42 @@ inline int mv_launch(mv_site at, dim3 grid, dim3 block, size_t lds, hipStream_t 
   return mv_check_launch(at);
 }
 
+// Workgroups of kernel K (`threads` per group, `lds` bytes of dynamic LDS) that are RESIDENT on the current device at once:
+// the grid of a grid-stride kernel whose register count limits occupancy.  A larger grid runs in rounds, and the last round
+// leaves most of the chip idle (LayerNorm backward: 1 024 groups against 768 resident ran 1.33 rounds, -22 %).  Remembered per
+// (K, device) like the grants of mv_grant_lds.
+template <auto K>
+inline int mv_resident_blocks(int threads, size_t lds) {
+  static std::atomic<int> n_[32] = {};
+  int d = 0;
+  const bool have = hipGetDevice(&d) == hipSuccess && d >= 0 && d < 32;
+  if (have) {
+    const int c = n_[d].load(std::memory_order_acquire);
+    if (c > 0) return c;
+  }
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K, threads, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
+  const int r = per_cu * mv_cu_count();
+  if (have) n_[d].store(r, std::memory_order_release);
+  return r;
+}
+
+// A run-time selector becomes a template argument: f(std::integral_constant<int, V>{}) for the V among Vs that equals v,
+// MV_ERR_UNSUPPORTED if none does.  mv_pick<0, 1, 2>(op, [&](auto OP) { return mv_launch<kernel<OP()>>(...); }).  Only the listed
+// values are instantiated.
+template <int... Vs, typename F>
+inline int mv_pick(int v, F&& f) {
+  int rc = MV_ERR_UNSUPPORTED;
+  (void)((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  return rc;
+}
+// element type of a dtype code, so a dtype is picked the same way: mv_pick<MV_F32, MV_BF16>(dtype, [&](auto D) { .. mv_elem_t<D()> .. })
+template <int DTYPE>
+using mv_elem_t = std::tuple_element_t<DTYPE, std::tuple<float, bf16_t, int8_t, _Float16>>;
+static_assert(MV_F32 == 0 && MV_BF16 == 1 && MV_I8 == 2 && MV_F16 == 3, "mv_elem_t lists the element types in dtype-code order");
+
 // Argument check.  It also CLEARS the runtime's sticky last-error: hipGetLastError() reports the last error of ANY
-// earlier runtime call on this thread (e.g. the host framework probing a pointer), which MV_CHECK_LAUNCH would
+// earlier runtime call on this thread (e.g. the host framework probing a pointer), which mv_check_launch would
 // otherwise mistake for a failed launch.  Every entry point runs at least one MV_REQUIRE before it launches.
 #define MV_REQUIRE(cond, code)    \
   do {                            \

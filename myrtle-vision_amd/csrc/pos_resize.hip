@@ -142,17 +142,14 @@ inline bool pr_caps_ok(int sh, int sw, int gh, int gw) {
 
 }  // namespace
 
-#define S_ ((hipStream_t)stream)
-
 extern "C" int mv_pos_resize_fwd(const float* pos, float* out, int sh, int sw, int gh, int gw, int D, mv_stream_t stream) {
   MV_REQUIRE(pr_dims_ok(sh, sw, gh, gw, D), MV_ERR_SHAPE);
   MV_REQUIRE(pr_caps_ok(sh, sw, gh, gw), MV_ERR_UNSUPPORTED);
   MV_REQUIRE(pos && out && mv_aligned16(pos) && mv_aligned16(out), MV_ERR_ALIGN);
   long blocks = (((long)gh * gw + 1) * (D / 4) + 255) / 256;
   if (blocks > 4096) blocks = 4096;              // grid-stride beyond
-  pos_resize_fwd_kernel<<<(int)blocks, 256, 0, S_>>>(pos, out, sh, sw, gh, gw, D, (float)sh / (float)gh, (float)sw / (float)gw);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<pos_resize_fwd_kernel>(MV_HERE, (int)blocks, 256, 0, (hipStream_t)stream, pos, out, sh, sw, gh, gw, D,
+                                          (float)sh / (float)gh, (float)sw / (float)gw);
 }
 
 extern "C" int mv_pos_resize_bwd(const float* dout, float* dpos, int accumulate, int sh, int sw, int gh, int gw, int D,
@@ -162,8 +159,6 @@ extern "C" int mv_pos_resize_bwd(const float* dout, float* dpos, int accumulate,
   MV_REQUIRE(dout && dpos && mv_aligned16(dout) && mv_aligned16(dpos), MV_ERR_ALIGN);
   const long grid = ((long)sh * sw + 1) * ((D + 127) / 128);
   MV_REQUIRE(grid <= 0x7fffffffL, MV_ERR_UNSUPPORTED);
-  pos_resize_bwd_kernel<<<(int)grid, 256, 0, S_>>>(dout, dpos, accumulate, sh, sw, gh, gw, D, (float)sh / (float)gh,
-                                                   (float)sw / (float)gw);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_launch<pos_resize_bwd_kernel>(MV_HERE, (int)grid, 256, 0, (hipStream_t)stream, dout, dpos, accumulate, sh, sw, gh, gw,
+                                          D, (float)sh / (float)gh, (float)sw / (float)gw);
 }

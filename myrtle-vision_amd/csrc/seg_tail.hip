@@ -210,8 +210,6 @@ constexpr size_t SEG_LDS_LIMIT = 64 * 1024;
 
 }  // namespace
 
-#define S_ ((hipStream_t)stream)
-
 extern "C" long mv_seg_ce_partials(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
   return (long)B * (((long)H * W + SEG_PX_PER_BLOCK - 1) / SEG_PX_PER_BLOCK);
@@ -223,16 +221,14 @@ extern "C" int mv_seg_ce_fwd(const float* small, const int64_t* labels, float* l
   const size_t lds = (size_t)h * w * C * sizeof(float);
   MV_REQUIRE(lds <= SEG_LDS_LIMIT, MV_ERR_UNSUPPORTED);
   MV_REQUIRE(B <= 65535, MV_ERR_SHAPE);
-  if (B == 0) {
-    mv_zero_f32_kernel<<<1, 64, 0, S_>>>(stats, 4);          // a kernel, not hipMemsetAsync: graph-capture safe (mv_cross_entropy)
-    return MV_OK;
-  }
+  hipStream_t s = (hipStream_t)stream;
+  // a kernel, not hipMemsetAsync: graph-capture safe (mv_cross_entropy)
+  if (B == 0) return mv_launch<mv_zero_f32_kernel>(MV_HERE, 1, 64, 0, s, stats, 4);
   const int bpi = (int)(((long)H * W + SEG_PX_PER_BLOCK - 1) / SEG_PX_PER_BLOCK);
-  seg_ce_fwd_kernel<<<dim3(bpi, B), 256, lds, S_>>>(small, labels, lse, pred, partials, C, h, w, H, W,
-                                                    (float)h / (float)H, (float)w / (float)W);
-  seg_ce_finish_kernel<<<1, 256, 0, S_>>>(partials, (long)bpi * B, 1.0f / ((float)B * (float)H * (float)W), stats);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  if (int rc = mv_launch<seg_ce_fwd_kernel>(MV_HERE, dim3(bpi, B), 256, lds, s, small, labels, lse, pred, partials, C, h, w, H, W,
+                                            (float)h / (float)H, (float)w / (float)W))
+    return rc;
+  return mv_launch<seg_ce_finish_kernel>(MV_HERE, 1, 256, 0, s, partials, (long)bpi * B, 1.0f / ((float)B * (float)H * (float)W), stats);
 }
 
 extern "C" int mv_seg_ce_bwd(const float* small, const int64_t* labels, const float* lse, const float* stats, void* dsmall,
@@ -245,12 +241,9 @@ extern "C" int mv_seg_ce_bwd(const float* small, const int64_t* labels, const fl
   MV_REQUIRE(lds <= SEG_LDS_LIMIT, MV_ERR_UNSUPPORTED);
   MV_REQUIRE(B <= 65535, MV_ERR_SHAPE);
   if (B == 0) return MV_OK;
-  if (ds_dtype == MV_BF16)
-    seg_ce_bwd_kernel<bf16_t><<<dim3(h, B), 256, lds, S_>>>(small, labels, lse, (bf16_t*)dsmall, ld_ds, grad_scale, stats, C, h,
-                                                            w, H, W, (float)h / (float)H, (float)w / (float)W);
-  else
-    seg_ce_bwd_kernel<float><<<dim3(h, B), 256, lds, S_>>>(small, labels, lse, (float*)dsmall, ld_ds, grad_scale, stats, C, h, w,
-                                                           H, W, (float)h / (float)H, (float)w / (float)W);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_pick<MV_F32, MV_BF16>(ds_dtype, [&](auto D) {
+    using T = mv_elem_t<D()>;
+    return mv_launch<seg_ce_bwd_kernel<T>>(MV_HERE, dim3(h, B), 256, lds, (hipStream_t)stream, small, labels, lse, (T*)dsmall, ld_ds,
+                                           grad_scale, stats, C, h, w, H, W, (float)h / (float)H, (float)w / (float)W);
+  });
 }

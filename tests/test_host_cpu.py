@@ -62,6 +62,24 @@ def test_library_exports_every_declared_symbol_with_matching_signature():
     assert handle.mv_layernorm_bwd_workspace_bytes(50432, 768) == 1024 * 3 * 768 * 4
 
 
+def test_every_launch_goes_through_mv_launch():
+    """One way to launch (mv_launch, the only <<< of csrc/) and one way to turn a run-time selector into a template argument
+    (mv_pick): the launch macros and the shared launch check they replaced stay gone."""
+    csrc = os.path.join(ROOT, "myrtle-vision_amd", "csrc")
+    retired = ["MV_CHECK_LAUNCH", "MV_RESIDENT_BLOCKS", "LN_GO", "LN_FWD_CASE", "LN_SPLIT_CASE", "LN_BWD_LAUNCH", "MV_F32_FAST",
+               "MV_F32_LAUNCH", "MV_QI8F", "MV_QI8", "S_"]
+    files = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)))     # csrc/diag/ is kept as a record, not built
+    assert len(files) >= 13
+    for f in files:
+        src = open(os.path.join(csrc, f)).read()
+        assert src.count("<<<") == (1 if f == "mv_common.h" else 0), f
+        for macro in retired:
+            assert not re.search(rf"\b{macro}\b", src), (f, macro)
+    common = open(os.path.join(csrc, "mv_common.h")).read()
+    assert re.search(r"inline int mv_launch\([^)]*\) \{[^}]*<<<[^}]*return mv_check_launch\(at\);", common, flags=re.S)
+    assert "inline int mv_pick(" in common and "inline int mv_resident_blocks(" in common
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from myrtle_vision.hip import lib
     monkeypatch.setattr(lib, "_lib", None)
