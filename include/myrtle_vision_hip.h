@@ -411,6 +411,38 @@ int mv_cross_entropy(const float* logits, const int64_t* labels, float* loss_sum
                      int ld_dl, int64_t* argmax, long outer, int C, long inner, float grad_scale,
                      mv_stream_t stream);
 
+/* ---- soft-target loss and batch mixing (csrc/mixup.hip).  The reference has neither: these replace what a timm-style recipe
+ * composes from torch ops -- timm.data.Mixup (batch mode: mixup_target's one_hot / flip / blend, and the image blend or box copy
+ * of Mixup._mix_batch) and timm.loss.SoftTargetCrossEntropy / LabelSmoothingCrossEntropy.  Sample i of a batch of B is paired
+ * with j = B - 1 - i (x.flip(0)); lam and the box are HOST scalars, so nothing is copied back and nothing synchronises. ----
+ * mv_cross_entropy_soft: logits fp32 [B, C] dense, labels int64 [B].  Target t_i = lam * s(y_i) + (1 - lam) * s(y_j) with
+ *   s(y) = eps / C everywhere plus (1 - eps) at class y; it is never materialised.  pair_flip = 0: no partner (y_j = y_i),
+ *   requires lam == 1.  lam = 1, eps = 0 is the plain mean cross entropy; eps > 0 alone is cross_entropy(label_smoothing=eps).
+ *   sample_loss: caller-provided fp32 [B] workspace, left holding  lse_i - (1-eps) * (lam * z[i,y_i] + (1-lam) * z[i,y_j])
+ *     - (eps/C) * sum_c z[i,c];  loss: fp32 [1] = their mean, by one fixed-order reduction in a second one-wave launch -- no
+ *   floating-point atomics, so loss and gradient are bitwise reproducible run to run.
+ *   dlogits (optional, fp32 [B, C]) = (softmax(z_i) - t_i) * grad_scale / B.  argmax (optional, int64 [B]): first index wins.
+ *   A label outside [0, C), the sample's own or its partner's, is never used as an index: that sample's loss and the mean are
+ *   NaN and its dlogits row is zero.  No ignore_index (classification only).  One wave per sample: any C >= 2.
+ *   MV_ERR_SHAPE: B < 0 or C < 2; MV_ERR_ALIGN: a null logits / labels / loss / sample_loss; MV_ERR_UNSUPPORTED: eps outside
+ *   [0, 1), lam outside [0, 1], or pair_flip == 0 with lam != 1.  B == 0: nothing is launched and no pointer is looked at, MV_OK.
+ * mv_mix_batch: x = dense [B, Ch, H, W] of `elem` (MV_F32 | MV_BF16, else MV_ERR_UNSUPPORTED), 16-byte aligned, mixed IN PLACE:
+ *   each of the B / 2 pairs is visited once and a thread owns the same element of both samples (reads both, then writes both).
+ *   For odd B the middle sample is its own partner and is not touched.
+ *   mode 0, Mixup: x_i' = lam * x_i + (1 - lam) * x_j and x_j' = lam * x_j + (1 - lam) * x_i in fp32, one rounding to `elem`;
+ *     16-byte accesses over the flat Ch * H * W extent wherever both samples sit at the same offset from a 16-byte boundary,
+ *     single elements elsewhere.  lam == 1 launches nothing.  The box is ignored.
+ *   mode 1, CutMix: rows [y0, y1) x columns [x0, x1) of every channel are swapped between x_i and x_j bit for bit; only the box
+ *     is read or written (the launch covers its rows alone).  An empty box launches nothing.  lam is ignored: the caller sets
+ *     lam = 1 - box_area / (H * W) for the loss.
+ *   MV_ERR_SHAPE: a dimension <= 0, B < 0, or not 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W (mode 1); MV_ERR_ALIGN: x null or not
+ *   16-byte aligned; MV_ERR_UNSUPPORTED: another mode, lam outside [0, 1] (mode 0), more than 65 535 pairs or Ch*H*W >= 2^31. */
+int mv_cross_entropy_soft(const float* logits, const int64_t* labels, float* loss, float* sample_loss, float* dlogits,
+                          int64_t* argmax, int B, int C, float lam, float eps, int pair_flip, float grad_scale,
+                          mv_stream_t stream);
+int mv_mix_batch(void* x, int elem, int B, int Ch, int H, int W, int mode, float lam, int y0, int y1, int x0, int x1,
+                 mv_stream_t stream);
+
 /* ---- bilinear upsample (align_corners=False): nn.Upsample(size, 'bilinear') vit.py:355,371 ----
  * small[b, c, y, x] is read at  small + b*sb + c*sc + (y*w + x)*sp  (so the [B, h*w, C] output of the decoder GEMM is
  * consumed in place: the reference's transpose/view, vit.py:367-369, costs nothing); big: fp32 [B, C, H, W] dense.

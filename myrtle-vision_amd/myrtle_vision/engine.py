@@ -232,6 +232,32 @@ def _fused_seg_tail(task, criterion):
     return task == "segmentation" and type(criterion) is CrossEntropyLoss
 
 
+_MIX_KEYS = ("label_smoothing", "mixup_alpha", "cutmix_alpha", "mixup_prob", "mixup_switch_prob")
+
+
+def _train_criterion(task, train_config):
+    """-> (training criterion, Mixup or None) from the optional ``train_config`` keys ``label_smoothing``, ``mixup_alpha``,
+    ``cutmix_alpha``, ``mixup_prob`` (default 1) and ``mixup_switch_prob`` (default 0.5): an extension, the reference has no such
+    recipe.  With smoothing and both alphas absent or zero this is the reference's ``CrossEntropyLoss()`` and no mixer, and
+    ``utils.mixup`` is not even imported; otherwise ``SoftTargetCrossEntropy`` and, with an alpha > 0, a ``Mixup``.  Classification
+    only: any of the keys on another task is an error."""
+    present = [k for k in _MIX_KEYS if k in train_config]
+    if present and task != "classification":
+        raise ValueError(f"train_config key {present[0]!r} is a classification recipe (label smoothing / Mixup / CutMix); "
+                         f"task={task!r} does not take it")
+    smoothing = float(train_config.get("label_smoothing", 0.0))
+    mixup_alpha, cutmix_alpha = float(train_config.get("mixup_alpha", 0.0)), float(train_config.get("cutmix_alpha", 0.0))
+    if smoothing == 0.0 and mixup_alpha == 0.0 and cutmix_alpha == 0.0:
+        return CrossEntropyLoss(), None
+    from myrtle_vision.hip.functional import SoftTargetCrossEntropy
+    mixer = None
+    if mixup_alpha > 0 or cutmix_alpha > 0:
+        from myrtle_vision.utils.mixup import Mixup
+        mixer = Mixup(mixup_alpha, cutmix_alpha, prob=float(train_config.get("mixup_prob", 1.0)),
+                      switch_prob=float(train_config.get("mixup_switch_prob", 0.5)))
+    return SoftTargetCrossEntropy(smoothing, return_argmax=True), mixer
+
+
 @torch.no_grad()
 def validation(val_loader, device, criterion, vit, task, num_classes):
     total_loss, total_acc, n = 0.0, 0.0, max(len(val_loader), 1)
@@ -258,6 +284,7 @@ def train_worker(rank, num_gpus, config, task="classification"):
         return _train_detection(rank, num_gpus, config)
     train_config, dist_config, vit_config = config["train_config"], config["dist_config"], config["vit_config"]
     data_config = parse_config(config["data_config_path"])
+    train_criterion, mixer = _train_criterion(task, train_config)      # first: a recipe key on the wrong task fails before any work
     if not torch.cuda.is_available():
         raise RuntimeError("training needs an MI355X: the myrtle_vision HIP path has no CPU fallback")
     device = torch.device("cuda", rank)
@@ -301,7 +328,8 @@ def train_worker(rank, num_gpus, config, task="classification"):
     optimizer_args = get_optimizer_args(train_config)
     optimizer = create_optimizer(optimizer_args, vit)
     lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
-    criterion = CrossEntropyLoss()
+    # validation keeps the plain criterion; without a recipe key it IS the training criterion, the reference's CrossEntropyLoss()
+    criterion = train_criterion if type(train_criterion) is CrossEntropyLoss else CrossEntropyLoss()
     iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer,
                                             lr_scheduler=lr_scheduler)
     optimizer.arena.bump_versions()
@@ -341,10 +369,16 @@ def train_worker(rank, num_gpus, config, task="classification"):
             reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
             if _fused_seg_tail(task, criterion):
                 loss, acc_t, _ = vit.segmentation_loss(imgs, labels)
-            else:
+            elif train_criterion is criterion:
                 outputs = vit(imgs)
                 loss = criterion(outputs, labels)
                 acc_t = None
+            else:                                                # label smoothing / Mixup / CutMix: each micro-batch within itself
+                lam = 1.0
+                if mixer is not None:
+                    imgs, lam = mixer(imgs, labels)              # in place; the labels stay the original ones
+                loss, pred = train_criterion(vit(imgs), labels, lam)
+                acc_t = (pred == labels).float().mean()          # the kernel's arg-max against the ORIGINAL labels
             loss.backward()
             n_accum += 1
             if clip_every and n_accum < n_batch_accum:

@@ -1053,6 +1053,51 @@ class CrossEntropyLoss(torch.nn.Module):
         return cross_entropy(logits, labels)
 
 
+class _SoftCrossEntropy(Function):
+    """Mean cross entropy against the Mixup / CutMix target with label smoothing (timm's ``SoftTargetCrossEntropy`` on
+    ``mixup_target``'s output, neither materialised), with the gradient and the arg-max produced in the same pass."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, logits, labels, lam, smoothing, pair_flip):
+        ops.require_cuda(logits, labels)
+        loss, dl, am, _ = ops.cross_entropy_soft(logits.float(), labels, lam, smoothing, pair_flip, want_grad=True, want_argmax=True)
+        ctx.save_for_backward(dl)
+        ctx.shape, ctx.dtype = logits.shape, logits.dtype
+        ctx.mark_non_differentiable(am)
+        return loss.view(()), am
+
+    @staticmethod
+    @_scoped
+    def backward(ctx, g, _g_argmax):
+        (dl,) = ctx.saved_tensors
+        return (dl.view(ctx.shape) * g).to(ctx.dtype), None, None, None, None
+
+
+def soft_cross_entropy(logits, labels, lam=1.0, smoothing=0.0, pair_flip=True, return_argmax=False):
+    """Mean of ``-sum_c t[i, c] * log_softmax(logits)[i, c]`` over the batch, ``t_i = lam * s(y_i) + (1 - lam) * s(y_j)`` with
+    ``j = B - 1 - i`` and ``s(y)`` = ``smoothing / C`` everywhere plus ``1 - smoothing`` at ``y``.  ``lam`` is a host scalar (what
+    ``utils.mixup.Mixup`` returns).  ``lam=1, smoothing=0`` is ``cross_entropy``.  ``return_argmax``: also the kernel's first-index
+    arg-max of every row (int64 [B]), so an accuracy needs no further pass over the logits."""
+    loss, am = _SoftCrossEntropy.apply(logits, labels, float(lam), float(smoothing), bool(pair_flip))
+    return (loss, am) if return_argmax else loss
+
+
+class SoftTargetCrossEntropy(torch.nn.Module):
+    """The training criterion of a Mixup / CutMix / label-smoothing recipe on the HIP kernel: ``forward(logits, labels, lam)`` with
+    the HARD labels of the batch and the ``lam`` its mixing drew -- timm's ``SoftTargetCrossEntropy`` without the [B, C] target.
+    ``return_argmax=True`` makes ``forward`` return ``(loss, argmax)``."""
+
+    def __init__(self, smoothing=0.0, return_argmax=False):
+        super().__init__()
+        if not 0.0 <= smoothing < 1.0:
+            raise ValueError(f"label smoothing must lie in [0, 1), got {smoothing}")
+        self.smoothing, self.return_argmax = float(smoothing), bool(return_argmax)
+
+    def forward(self, logits, labels, lam=1.0):
+        return soft_cross_entropy(logits, labels, lam, self.smoothing, True, self.return_argmax)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # fake quantisation with straight-through gradient (utils/quantize.py:77-89)
 # ------------------------------------------------------------------------------------------------------------

@@ -1472,6 +1472,48 @@ def cross_entropy(logits, labels, *, want_grad, grad_dtype=torch.float32, ld_dl=
     return loss, dl, am
 
 
+def cross_entropy_soft(logits, labels, lam=1.0, smoothing=0.0, pair_flip=True, want_grad=False, want_argmax=False,
+                       grad_scale=1.0):
+    """Mean soft-target CE of Mixup / CutMix and label smoothing (mv_cross_entropy_soft): logits fp32 [B, C], labels int64 [B];
+    sample i is paired with B-1-i and its target is ``lam * s(y_i) + (1-lam) * s(y_j)``, ``s`` = one-hot smoothed by ``smoothing``.
+    ``lam`` is a host scalar.  -> (loss[1], dlogits|None, argmax|None, per-sample losses [B])"""
+    require_cuda(logits, labels)
+    if logits.dim() != 2 or labels.shape != logits.shape[:1]:
+        raise RuntimeError(f"cross_entropy_soft: logits [B, C] and labels [B] expected, got {tuple(logits.shape)} and "
+                           f"{tuple(labels.shape)}")
+    if logits.dtype != torch.float32:
+        raise RuntimeError("cross_entropy_soft: fp32 logits expected")
+    logits = logits.contiguous()
+    labels = labels.contiguous()
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    B, C = logits.shape
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    per_sample = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dl = torch.empty(B, C, dtype=torch.float32, device=logits.device) if want_grad else None
+    am = torch.empty(B, dtype=torch.int64, device=logits.device) if want_argmax else None
+    check(lib().mv_cross_entropy_soft(_p(logits), _p(labels), _p(loss), _p(per_sample), _p(dl), _p(am), B, C, float(lam),
+                                      float(smoothing), int(bool(pair_flip)), float(grad_scale), _s()),
+          "cross_entropy_soft", B=B, C=C, lam=lam, smoothing=smoothing, pair_flip=bool(pair_flip))
+    return loss, dl, am, per_sample
+
+
+def mix_batch(x, *, lam=None, box=None):
+    """Mixup (``lam``) or CutMix (``box`` = (y0, y1, x0, x1)) of a dense [B, Ch, H, W] fp32 / bf16 batch IN PLACE
+    (mv_mix_batch): sample i with sample B-1-i.  Both arguments are host scalars.  -> x"""
+    require_cuda(x)
+    if (lam is None) == (box is None):
+        raise ValueError("mix_batch: exactly one of lam (Mixup) and box (CutMix) is given")
+    if x.dim() != 4 or not x.is_contiguous() or x.dtype not in _DT:
+        raise RuntimeError("mix_batch: a contiguous [B, Ch, H, W] fp32 or bf16 batch expected "
+                           f"(got {tuple(x.shape)}, {x.dtype}, contiguous={x.is_contiguous()})")
+    B, Ch, H, W = x.shape
+    mode, y0, y1, x0, x1 = (0, 0, 0, 0, 0) if box is None else (1, *(int(v) for v in box))
+    check(lib().mv_mix_batch(_p(x), _DT[x.dtype], B, Ch, H, W, mode, 1.0 if lam is None else float(lam), y0, y1, x0, x1, _s()),
+          "mix_batch", B=B, Ch=Ch, H=H, W=W, mode=mode, lam=lam, box=box)
+    return x
+
+
 def upsample_bilinear_fwd(small, sb, sc, sp, B, C, h, w, H, W):
     big = torch.empty(B, C, H, W, dtype=torch.float32, device=small.device)
     check(lib().mv_upsample_bilinear_fwd(_p(small), sb, sc, sp, _p(big), B, C, h, w, H, W, _s()), "upsample_fwd",
