@@ -99,6 +99,11 @@ def same_bits(a, b):
 ROUTING_MULT = {64: 8.0, 32: 16.0, 128: 8.0}     # k = mult * r with r = +-1: exact in bf16 and half
 ROUTING_MIN_GAP = {64: 128.0, 32: 104.0, 128: 104.0}   # score units; exp(-104) < 2^-149, the smallest fp32 subnormal
 ROUTING_CASES = ([(64, n) for n in EDGES] + [(64, 577), (64, 1025)] + [(32, 197), (32, 577), (128, 197), (128, 577)])
+# the key-tiled kernels called directly at their block edges (tests/test_attention_tiled.py)
+TILED_EDGES = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 320, 321, 383, 384, 385, 511, 512, 513]
+TILED_EDGES_DH = {32: [1, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513],      # 256 rows per workgroup
+                  128: [1, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 385]}
+ROUTING_CASES += [(64, n) for n in TILED_EDGES if n not in EDGES] + [(dh, n) for dh in (32, 128) for n in TILED_EDGES_DH[dh]]
 
 
 def routing_inputs(B, N, H, dh=64):
@@ -169,28 +174,29 @@ def test_routing_builder_gives_an_exact_permutation_softmax(dh, N):
 DISTS = ("plain", "peaked", "offset")
 
 
-def random_inputs(family, dist, B, N, H, seed=1):
-    """qkv [B, N, 3*H*64] ROUNDED to the family's operand type (held in fp32) and dout (bf16-rounded for bf16).  plain: the inputs
+def random_inputs(family, dist, B, N, H, seed=1, dh=64):
+    """qkv [B, N, 3*H*dh] ROUNDED to the family's operand type (held in fp32) and dout (bf16-rounded for bf16).  plain: the inputs
     of tests/test_hip_ops.py; peaked: q and k times 4 (a few keys dominate each row); offset: 5.0 added to every feature of every
-    key and query (|c|^2 * scale = 200: every score sits near +200 and only the max subtraction keeps exp finite)."""
+    key and query (|c|^2 * scale = 200: every score sits near +200 and only the max subtraction keeps exp finite; at another width
+    the constant that keeps that 200: c = sqrt(200 / sqrt(dh)))."""
     std = 1.2 if family == "half" else 1.5
-    x = (torch.randn(B, N, 3, H, 64, generator=g(seed)) * std)
+    x = (torch.randn(B, N, 3, H, dh, generator=g(seed)) * std)
     if dist == "peaked":
         x[:, :, :2] *= 4.0
     elif dist == "offset":
-        x[:, :, :2] += 5.0
-    dout = torch.randn(B, N, H * 64, generator=g(seed + 1))
-    x = x.view(B, N, 3 * H * 64).to(OPERAND[family]).float()
+        x[:, :, :2] += math.sqrt(200.0 / math.sqrt(dh))       # 5.0 at 64
+    dout = torch.randn(B, N, H * dh, generator=g(seed + 1))
+    x = x.view(B, N, 3 * H * dh).to(OPERAND[family]).float()
     if family == "bf16":
         dout = dout.to(torch.bfloat16).float()
     return x, dout
 
 
-def exact_fp64(qkv, dout, H):
+def exact_fp64(qkv, dout, H, dh=64):
     """fp64 autograd on the given (already rounded) inputs -> out, lse, dqkv"""
     ref = qkv.double().requires_grad_(True)
-    q, k, v = split_qkv(ref, H)
-    s = (q @ k.transpose(-2, -1)) * SCALE
+    q, k, v = split_qkv(ref, H, dh)
+    s = (q @ k.transpose(-2, -1)) * dh ** -0.5
     out = unheads(s.softmax(-1) @ v)
     out.backward(dout.double())
     return out.detach(), torch.logsumexp(s.detach(), -1), ref.grad
@@ -207,7 +213,7 @@ LOG2E32 = float(torch.tensor(1.4426950408889634, dtype=torch.float32))
 LN2_32 = float(torch.tensor(0.6931471805599453, dtype=torch.float32))
 
 
-def emulate(family, qkv, dout, H, rounded=True):
+def emulate(family, qkv, dout, H, rounded=True, dh=64, blockwise=False):
     """The kernels' rounding model in plain torch -> out, lse, dqkv (fp64 tensors holding the rounded values).
 
     All three families work in log2 units: the raw fp32 score sum times sl2 = fp32(scale * log2(e)), rounded; the forward takes
@@ -220,15 +226,25 @@ def emulate(family, qkv, dout, H, rounded=True):
     the softmax scale.  half: O stays fp32; dO is multiplied by a power of two per (image, head) and rounded to half, delta uses the
     rounded dO, dS is formed without the softmax scale (applied to the fp32 dQ / dK), the power of two is divided out at the end.
     fp32 (csrc/attention_f32.hip): nothing is rounded below fp32.
-    rounded=False: no rounding at all -- the model must then reproduce fp64 autograd."""
+    rounded=False: no rounding at all -- the model must then reproduce fp64 autograd.
+    dh: the head width (bf16 only beyond 64); the softmax scale is fp32(dh^-0.5), as the entry points receive it.
+    blockwise=True: the key-tiled kernels (attn_fwd_kernel of csrc/attention_tiled.hip, attn_fwd_long_f32_kernel of
+    csrc/attention_f32.hip).  Their backward has the whole-head kernels' roundings (P rebuilt from the saved lse, 32 consecutive
+    rows per 16x16x32 instruction, fp32: rows 16 T + 4 g + r) except delta of the fp32 family, which attn_delta_long_f32_kernel
+    sums as the half prep kernel does: four features per thread, a 16-thread tree.  Their forward is an online softmax over
+    64-key blocks: per block the maximum mb of the block's scores, mn = max(m, mb), alpha = exp2(m - mn) (0 on the first block),
+    P = exp2(s2 - mn) against the RUNNING maximum, l_g = fp32(l_g * alpha) + the block's P in key order for each of the four lane
+    groups g (key j of the block sits in group (j >> 2) & 3), O = fp32(O * alpha), then O += P.V of the block with P rounded to
+    the operand type; at the end l = (l_0 + l_1) + (l_2 + l_3), O = fp32(O * fp32(1 / l)) (a rounded reciprocal, not a division)
+    and lse = fp32(fp32(m + log2(l)) * ln(2))."""
     if not rounded:
         op = f32 = lambda x: x                                                   # noqa: E731
     else:
         op = lambda x: x.to(OPERAND[family]).double()                            # noqa: E731
         f32 = lambda x: x.float().double()                                       # noqa: E731
 
-    def mm(a, b, over="features"):
-        """a @ b as the matrix instructions accumulate it.  bf16 / half: 16x16x32 -- the 32 products of an instruction (exact in
+    def mm(a, b, over="features", acc=None):
+        """a @ b (+ acc) as the matrix instructions accumulate it.  bf16 / half: 16x16x32 -- the 32 products of an instruction (exact in
         fp32) are summed before the one rounding into the accumulator, 32 consecutive indices of the contraction per instruction.
         fp32: 16x16x4 with the four lane groups as its contraction, one fp32 rounding per product, in the kernel's order --
         features 16 c + 4 g + kk for (c, kk, g) (load_global / load_rows of attention_f32.hip), keys or queries 16 T + 4 g + r for
@@ -236,7 +252,7 @@ def emulate(family, qkv, dout, H, rounded=True):
         in another grouping has errors of the same size but not the same errors, and a slice of few rows shows the difference
         (measured: the half kernel at N = 16 sits at 2.78x a sequential sum's error and at 1.01x this one's)."""
         if not rounded:
-            return a @ b
+            return a @ b if acc is None else acc + a @ b
         K = a.shape[-1]
         if family != "fp32":
             groups = [list(range(i, min(i + 32, K))) for i in range(0, K, 32)]
@@ -244,24 +260,46 @@ def emulate(family, qkv, dout, H, rounded=True):
             groups = [[16 * c + 4 * gg + kk] for c in range(4) for kk in range(4) for gg in range(4)]
         else:
             groups = [[i] for t in range((K + 15) // 16) for r in range(4) for i in (16 * t + 4 * gg + r for gg in range(4)) if i < K]
-        acc = torch.zeros(a.shape[:-1] + (b.shape[-1],), dtype=torch.float64)
+        if acc is None:
+            acc = torch.zeros(a.shape[:-1] + (b.shape[-1],), dtype=torch.float64)
         for idx in groups:
             if idx:
                 acc = f32(acc + a[..., idx] @ b[..., idx, :])
         return acc
 
-    q, k, v = split_qkv(qkv.double(), H)
-    do = heads(dout.double(), H)
-    sl2 = float(f32(torch.tensor(float(torch.tensor(SCALE, dtype=torch.float32)) * LOG2E32, dtype=torch.float64))) if rounded \
-        else SCALE * math.log2(math.e)
+    q, k, v = split_qkv(qkv.double(), H, dh)
+    do = heads(dout.double(), H, dh)
+    scale = float(torch.tensor(dh ** -0.5, dtype=torch.float32)) if rounded else dh ** -0.5      # (64: 0.125 either way)
+    sl2 = float(f32(torch.tensor(scale * LOG2E32, dtype=torch.float64))) if rounded else scale * math.log2(math.e)
     log2e, ln2 = (LOG2E32, LN2_32) if rounded else (math.log2(math.e), math.log(2.0))
     raw = mm(q, k.transpose(-2, -1))
     s2 = f32(raw * sl2)
-    m = s2.amax(-1, keepdim=True)
-    p = f32(torch.exp2(f32(s2 - m)))
-    l = p.sum(-1, keepdim=True)
+    if blockwise:
+        N = s2.shape[-1]
+        m = torch.full(s2.shape[:-1] + (1,), -math.inf, dtype=torch.float64)
+        lg = torch.zeros(s2.shape[:-1] + (4,), dtype=torch.float64)
+        o = torch.zeros_like(q)
+        for k0 in range(0, N, 64):
+            blk = slice(k0, min(k0 + 64, N))
+            mn = torch.maximum(m, s2[..., blk].amax(-1, keepdim=True))
+            alpha = f32(torch.exp2(f32(m - mn)))
+            m = mn
+            p = f32(torch.exp2(f32(s2[..., blk] - mn)))
+            lg = f32(lg * alpha)
+            for kt in range(0, p.shape[-1], 16):               # a lane adds its keys 16 kt + 4 g + r in the order (kt, r)
+                for r in range(4):
+                    cols = [kt + 4 * gg + r for gg in range(4)]
+                    live = [c for c in cols if c < p.shape[-1]]
+                    lg[..., :len(live)] = f32(lg[..., :len(live)] + p[..., live])
+            o = mm(op(p), v[..., blk, :], "rows", acc=f32(o * alpha))
+        l = f32(f32(lg[..., 0:1] + lg[..., 1:2]) + f32(lg[..., 2:3] + lg[..., 3:4]))
+        out = f32(o * f32(1.0 / l))
+    else:
+        m = s2.amax(-1, keepdim=True)
+        p = f32(torch.exp2(f32(s2 - m)))
+        l = p.sum(-1, keepdim=True)
+        out = f32(mm(op(p), v, "rows") / l)
     lse = f32(f32(m + torch.log2(l)) * ln2)
-    out = f32(mm(op(p), v, "rows") / l)
     if family == "bf16":
         out = op(out)
     gs = None
@@ -272,7 +310,7 @@ def emulate(family, qkv, dout, H, rounded=True):
     x = do * out                                           # (products of two fp32 values: exact here)
     if not rounded:
         delta = x.sum(-1, keepdim=True)
-    elif family == "fp32":                                 # attn_bwd_f32_kernel: an fma chain per lane group, then two shuffles
+    elif family == "fp32" and not blockwise:               # attn_bwd_f32_kernel: an fma chain per lane group, then two shuffles
         part = []
         for gg in range(4):
             acc = torch.zeros_like(x[..., 0])
@@ -281,7 +319,7 @@ def emulate(family, qkv, dout, H, rounded=True):
                     acc = f32(acc + x[..., 16 * c + 4 * gg + e])
             part.append(acc)
         delta = f32(f32(part[0] + part[1]) + f32(part[2] + part[3])).unsqueeze(-1)
-    elif family == "half":                                 # attn_bwd_prep_f16_kernel: four features per thread, a 16-thread tree
+    elif family in ("half", "fp32"):                       # attn_bwd_prep_f16_kernel: four features per thread, a 16-thread tree
         part = [f32(f32(f32(f32(x[..., 4 * t]) + x[..., 4 * t + 1]) + x[..., 4 * t + 2]) + x[..., 4 * t + 3]) for t in range(16)]
         while len(part) > 1:
             part = [f32(part[i] + part[i + 1]) for i in range(0, len(part), 2)]
@@ -292,9 +330,9 @@ def emulate(family, qkv, dout, H, rounded=True):
     dp = mm(do, v.transpose(-2, -1))
     if family == "half":
         ds = op(f32(p * f32(dp - delta)))
-        dq, dk = mm(ds, k, "rows") * SCALE, mm(ds.transpose(-2, -1), q, "rows") * SCALE
+        dq, dk = mm(ds, k, "rows") * scale, mm(ds.transpose(-2, -1), q, "rows") * scale
     else:
-        ds = op(f32(f32(p * f32(dp - delta)) * SCALE))
+        ds = op(f32(f32(p * f32(dp - delta)) * scale))
         dq, dk = mm(ds, k, "rows"), mm(ds.transpose(-2, -1), q, "rows")
     dv = mm(op(p).transpose(-2, -1), do, "rows")
     if gs is not None:
@@ -304,35 +342,52 @@ def emulate(family, qkv, dout, H, rounded=True):
     return unheads(out), lse.squeeze(-1), dqkv
 
 
-def zero_gradient_bound(qkv, dout, H):
+def zero_gradient_bound(qkv, dout, H, dh=64):
     """N = 1: softmax is the constant 1, dq = dk = 0 exactly, and relative errors mean nothing.  What a kernel may leave is the
     difference of two fp32 sums of the same 64 products dO_d v_d taken in different orders (dP and delta), times |k| or |q| and the
-    scale: |dq|, |dk| <= 64 * 2^-23 * sum_d |dO_d v_d| * scale * max |q or k| per (image, head)."""
-    q, k, v = split_qkv(qkv.double(), H)
-    s = (heads(dout.double(), H).abs() * v.abs()).sum(-1).amax(-1)                       # [B, H]
-    return 64 * 2.0 ** -23 * s * SCALE * torch.maximum(q.abs().amax((2, 3)), k.abs().amax((2, 3)))
+    scale: |dq|, |dk| <= dh * 2^-23 * sum_d |dO_d v_d| * scale * max |q or k| per (image, head)."""
+    q, k, v = split_qkv(qkv.double(), H, dh)
+    s = (heads(dout.double(), H, dh).abs() * v.abs()).sum(-1).amax(-1)                   # [B, H]
+    return dh * 2.0 ** -23 * s * dh ** -0.5 * torch.maximum(q.abs().amax((2, 3)), k.abs().amax((2, 3)))
 
 
-def slice_err(got, want, H):
+def slice_err(got, want, H, dh=64):
     """L2 relative error of dq, dk, dv per (image, head): [3, B, H]"""
-    a, b = torch.stack(tuple(split_qkv(got.double().cpu(), H))), torch.stack(tuple(split_qkv(want.double(), H)))
+    a, b = torch.stack(tuple(split_qkv(got.double().cpu(), H, dh))), torch.stack(tuple(split_qkv(want.double(), H, dh)))
     return (a - b).flatten(3).norm(dim=3) / b.flatten(3).norm(dim=3).clamp_min(1e-300)
 
 
-def forward_bound(family, qkv, H):
-    """|out - want| <= ((2 u_P + u_out) + 64 * 2^-23 * max_k sum_d |q_d k_d| * scale) * max_k |v_k| per (image, query, head, feature):
-    P rounded once (and, in the row sum, not at all: twice u_P covers a truncating pack), the output rounded once, the fp32 score sum."""
-    q, k, v = split_qkv(qkv.double(), H)
-    ssum = (q.abs() @ k.abs().transpose(-2, -1)).amax(-1, keepdim=True) * SCALE          # [B, H, N, 1]
-    vmax = v.abs().amax(2, keepdim=True)                                                 # [B, H, 1, 64]
-    return unheads((2 * U_P[family] + U_OUT[family] + 64 * 2.0 ** -23 * ssum) * vmax)
+def forward_bound(family, qkv, H, dh=64, blocks=0):
+    """|out - want| <= ((2 u_P + u_out) + dh * 2^-23 * max_k sum_d |q_d k_d| * scale) * max_k |v_k| per (image, query, head, feature):
+    P rounded once (and, in the row sum, not at all: twice u_P covers a truncating pack), the output rounded once, the fp32 score sum.
+
+    blocks = ceil(N / 64) > 0: the online form of the key-tiled kernels.  P is rounded against the running maximum instead of the
+    final one, but a rounding to the operand type is relative, so its term is unchanged: the later factors alpha multiply the
+    rounded value.  The error of alpha itself multiplies O and l alike and leaves O / l.  What the online form adds, relative
+    to the running |O| <= l * max |v| (every P is positive, so running sums never exceed final ones):
+        per block   2^-24 * (1 [O * alpha] + 2 [the block's two accumulating P.V instructions] + 1 [l * alpha] + 16 [the lane's 16
+                    additions to l])                                                                          = 20 * 2^-24
+        at the end  2^-24 * (2 [the two shuffle additions of l] + 1 [1 / l rounded] + 1 [O * (1 / l) rounded])  =  4 * 2^-24
+    so the bound grows by (20 * blocks + 4) * 2^-24 * max |v|."""
+    q, k, v = split_qkv(qkv.double(), H, dh)
+    ssum = (q.abs() @ k.abs().transpose(-2, -1)).amax(-1, keepdim=True) * dh ** -0.5     # [B, H, N, 1]
+    vmax = v.abs().amax(2, keepdim=True)                                                 # [B, H, 1, dh]
+    online = (20 * blocks + 4) * 2.0 ** -24 if blocks else 0.0
+    return unheads((2 * U_P[family] + U_OUT[family] + dh * 2.0 ** -23 * ssum + online) * vmax)
 
 
-def lse_bound(qkv, H, lse):
-    """the fp32 score sum, then four fp32 roundings of a value of the size of the lse"""
-    q, k, _ = split_qkv(qkv.double(), H)
-    ssum = (q.abs() @ k.abs().transpose(-2, -1)).amax(-1) * SCALE
-    return 64 * 2.0 ** -23 * ssum + 4 * 2.0 ** -24 * lse.abs()
+def lse_bound(qkv, H, lse, dh=64, blocks=0):
+    """the fp32 score sum, then four fp32 roundings of a value of the size of the lse.
+    blocks = ceil(N / 64) > 0: the online form.  lse = (m + log2(l)) ln 2 with a running sum l.  A relative error of l is that
+    absolute error of ln(l); what the online form adds to it, in units of 2^-24:
+        per block   1 [l * alpha rounded] + 1 [exp2 of alpha] + 1 [the rounding of m - mn, an error of the exponent of
+                    2^-24 |m - mn| ln 2 weighted by alpha = 2^-|m - mn|: at most 0.53] + 16 [the lane's additions]     = 19
+        at the end  2 [the two shuffle additions]
+    (here alpha's own error does not cancel: there is no quotient)."""
+    q, k, _ = split_qkv(qkv.double(), H, dh)
+    ssum = (q.abs() @ k.abs().transpose(-2, -1)).amax(-1) * dh ** -0.5
+    online = (19 * blocks + 2) * 2.0 ** -24 if blocks else 0.0
+    return dh * 2.0 ** -23 * ssum + 4 * 2.0 ** -24 * lse.abs() + online
 
 
 @pytest.mark.parametrize("family", FAMILIES)
