@@ -1,10 +1,15 @@
 """CPU: the one place an attention kernel family is chosen (``ops.attention_path``), the pairing of forward and backward wrappers
 behind ``ops.attention_forward`` / ``ops.attention_backward`` as ``functional.attention_core`` and the fused attention block drive
-them, and the agreement of the Python length caps with the argument checks of the built library."""
+them, the agreement of the Python length caps with the argument checks of the built library, and -- per kernel family -- the
+``*_supported`` predicates at their caps and under the A/B switch, the bindings of the key-tiled entry points, the argument checks
+that run before any device work (the 64-wide families; tests/test_attention_dh_dispatch.py has the widths 32 and 128)."""
 import itertools
+from contextlib import nullcontext
 
 import pytest
 import torch
+
+from test_attention_short import MV_ERR_ALIGN, MV_ERR_SHAPE, MV_ERR_UNSUPPORTED, MV_OK
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -300,7 +305,7 @@ def test_attn_block_pairs_forward_and_backward(ops, recorded, block, monkeypatch
 # ------------------------------------------------------------------------------------------------------------
 # the caps of ops.py against the argument checks of the library (built library, no device: B = 0 launches nothing)
 # ------------------------------------------------------------------------------------------------------------
-OK, SHAPE, UNSUPPORTED = 0, -1, -4
+OK, SHAPE, UNSUPPORTED = MV_OK, MV_ERR_SHAPE, MV_ERR_UNSUPPORTED
 ADDR = 1 << 20                                               # 16-byte aligned, never read: every entry returns at B == 0
 INTS = {                                                     # the int arguments of each signature shape, in order
     "std": lambda N, dh: [0, N, 2],                         # B, N, H
@@ -363,3 +368,124 @@ def test_the_prep_helper_keeps_the_shape_tools_call_it_with(ops):
     """tools/bench_attn_long.py times the half backward's memory pass on its own: ``ops._attention_bwd_prep_f16(out, dout, B, N, H)``."""
     import inspect
     assert list(inspect.signature(ops._attention_bwd_prep_f16).parameters) == ["out", "dout", "B", "N", "H"]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# per family: the *_supported predicates, the bindings, the argument checks
+# ------------------------------------------------------------------------------------------------------------
+# family -> its predicate, the q/k/v dtype and head width it answers for, the segment scope it needs (half: the bf16x3h scope)
+PREDICATE = {"bf16": ("attention_fused_supported", BF16, 64, None), "half": ("attention_f16_supported", F32, 64, 4),
+             "fp32": ("attention_f32_fused_supported", F32, 64, None)}
+FUSED_N = {"bf16": [1, 197, 257, 320, 321, 577, 785, 1025, 4097, 8192], "half": [1, 197, 257, 288, 289, 321, 577, 1025, 4097, 8192],
+           "fp32": [1, 197, 272, 273, 577, 1025, 4097, 8192]}
+
+
+def holds(ops, monkeypatch, rows):
+    """rows of (ATTN_LONG, segment scope or None, predicate, dtype, N, head width, expected)"""
+    for long_on, scope, pred, dtype, N, w, want in rows:
+        monkeypatch.setattr(ops, "ATTN_LONG", long_on)
+        with ops.segments(scope) if scope else nullcontext():
+            assert bool(getattr(ops, pred)(dtype, N, w)) == want, (long_on, scope, pred, dtype, N, w)
+
+
+@pytest.mark.parametrize("family,N", [(f, n) for f, ns in FUSED_N.items() for n in ns])
+def test_attention_is_fused_up_to_the_cap(ops, monkeypatch, family, N):
+    pred, dtype, w, scope = PREDICATE[family]
+    holds(ops, monkeypatch, [(True, scope, pred, dtype, N, w, True)])
+
+
+FUSED, F16, F32_FUSED = (PREDICATE[f][0] for f in ("bf16", "half", "fp32"))
+# past the cap, another width, another dtype; then ATTN_LONG off, the A/B tools' materialised arm: the whole-head caps
+LIMITS = {
+    "bf16": [(True, None, FUSED, BF16, 8193, 64, False), (True, None, FUSED, BF16, 577, 32, False),
+             (True, None, FUSED, F32, 577, 64, False),            # fp32 / bf16x3 / bf16x3h keep their paths
+             (False, None, FUSED, BF16, 320, 64, True), (False, None, FUSED, BF16, 321, 64, False)],
+    "half": [(True, 4, F16, F32, 8193, 64, False), (True, 4, F16, F32, 577, 32, False), (True, 4, F16, BF16, 577, 64, False),
+             (False, 4, F16, F32, 288, 64, True), (False, 4, F16, F32, 289, 64, False), (False, 4, F16, F32, 577, 64, False)] +
+            [(True, nseg, F16, F32, N, 64, False) for nseg in (3, 6) for N in (577, 197)],   # outside the half-attention scope
+    "fp32": [(True, None, F32_FUSED, F32, 8193, 64, False), (True, None, F32_FUSED, F32, 577, 32, False),
+             (True, None, F32_FUSED, BF16, 577, 64, False), (False, None, F32_FUSED, F32, 272, 64, True),
+             (False, None, F32_FUSED, F32, 273, 64, False), (False, None, F32_FUSED, F32, 577, 64, False)],
+}
+# what a family's arrival left alone in the families before it
+UNCHANGED = {
+    "half": [(True, None, FUSED, F32, 577, 64, False), (True, 4, FUSED, F32, 577, 64, False)],
+    "fp32": [(True, None, FUSED, BF16, 577, 64, True), (True, None, FUSED, F32, 577, 64, False), (True, 4, F16, F32, 577, 64, True),
+             (True, 3, F16, F32, 577, 64, False), (True, 6, F16, F32, 577, 64, False),
+             (False, None, FUSED, BF16, 320, 64, True), (False, None, FUSED, BF16, 321, 64, False),
+             (False, 4, F16, F32, 288, 64, True), (False, 4, F16, F32, 289, 64, False)],
+}
+
+
+@pytest.mark.parametrize("family", list(LIMITS))
+def test_attention_limits_and_the_ab_switch(ops, monkeypatch, family):
+    holds(ops, monkeypatch, LIMITS[family])
+
+
+@pytest.mark.parametrize("family", list(UNCHANGED))
+def test_the_earlier_families_dispatch_is_unchanged(ops, monkeypatch, family):
+    holds(ops, monkeypatch, UNCHANGED[family])
+
+
+BOUND = {"bf16": {"mv_attention_fwd_long": None, "mv_attention_bwd_long": "ppppppp" "iii" "f" "p"},
+         "half": {"mv_attention_fwd_long_f16": "ppp" "iii" "f" "p", "mv_attention_bwd_long_f16": "pppppp" "ipp" "iii" "f" "p"},
+         "fp32": {"mv_attention_fwd_long_f32": "ppp" "iii" "f" "p", "mv_attention_fwd_long_f32_q8": "pp" "iii" "f" "f" "i" "p",
+                  "mv_attention_bwd_long_f32": "pppppp" "iii" "f" "p"}}
+
+
+@pytest.mark.parametrize("family", list(BOUND))
+def test_key_tiled_entry_points_are_bound(family):
+    from myrtle_vision.hip import lib
+    handle = lib.lib()
+    for name, kinds in BOUND[family].items():
+        assert kinds is None or lib.SIGNATURES[name][0] == kinds
+        assert getattr(handle, name) is not None
+
+
+def test_long_half_entry_points_reject_bad_arguments():
+    """Argument checks run before any device work: shapes past the cap, a bad segment count and misaligned or missing pointers."""
+    from myrtle_vision.hip import lib
+    L = lib.lib()
+    a = ADDR                                          # never dereferenced (rejected first)
+    assert L.mv_attention_fwd_long_f16(a, a, a, 1, 8193, 1, 0.125, None) == MV_ERR_SHAPE
+    assert L.mv_attention_fwd_long_f16(a, a, a, 1, 0, 1, 0.125, None) == MV_ERR_SHAPE
+    assert L.mv_attention_fwd_long_f16(a + 2, a, a, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN
+    bwd = L.mv_attention_bwd_long_f16
+    assert bwd(a, a, a, a, a, a, 0, None, None, 1, 8193, 1, 0.125, None) == MV_ERR_SHAPE
+    assert bwd(a, a, a, a, a, a, 4, None, None, 1, 577, 1, 0.125, None) == MV_ERR_UNSUPPORTED
+    assert bwd(a, a + 8, a, a, a, a, 3, None, None, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN
+    assert bwd(a, a, a, a, a, a, 6, a, None, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN      # colsum without its workspace
+    # B = 0 is a no-op that launches nothing
+    assert L.mv_attention_fwd_long_f16(a, a, a, 0, 577, 1, 0.125, None) == MV_OK
+    assert bwd(a, a, a, a, a, a, 0, a, a, 0, 577, 1, 0.125, None) == MV_OK
+
+
+def test_long_fp32_entry_points_reject_bad_arguments():
+    """Argument checks run before any device work: lengths past the cap, a bad quantiser, misaligned pointers and a missing lse or
+    delta workspace."""
+    from myrtle_vision.hip import lib
+    L = lib.lib()
+    a = ADDR                                          # never dereferenced (rejected first)
+    fwd, q8, bwd = L.mv_attention_fwd_long_f32, L.mv_attention_fwd_long_f32_q8, L.mv_attention_bwd_long_f32
+    assert fwd(a, a, a, 1, 8193, 1, 0.125, None) == MV_ERR_UNSUPPORTED
+    assert fwd(a, a, None, 1, 8193, 1, 0.125, None) == MV_ERR_UNSUPPORTED
+    assert fwd(a, a, a, 1, 0, 1, 0.125, None) == MV_ERR_SHAPE
+    assert fwd(a, a, a, -1, 577, 1, 0.125, None) == MV_ERR_SHAPE
+    assert fwd(a + 4, a, a, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN
+    assert fwd(a, a + 8, None, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN
+    assert q8(a, a, 1, 8193, 1, 0.125, 0.05, 128, None) == MV_ERR_UNSUPPORTED
+    assert q8(a, a, 1, 577, 1, 0.125, 0.05, 256, None) == MV_ERR_UNSUPPORTED
+    assert q8(a, a, 1, 577, 1, 0.125, 0.05, -1, None) == MV_ERR_UNSUPPORTED
+    assert q8(a, a, 1, 577, 1, 0.125, 0.0, 128, None) == MV_ERR_SHAPE
+    assert q8(a, a + 2, 1, 577, 1, 0.125, 0.05, 128, None) == MV_ERR_ALIGN
+    assert bwd(a, a, a, a, a, a, 1, 8193, 1, 0.125, None) == MV_ERR_UNSUPPORTED
+    assert bwd(a, a, a, a, a, a, 1, 0, 1, 0.125, None) == MV_ERR_SHAPE
+    assert bwd(a, a + 4, a, a, a, a, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN
+    assert bwd(a, a, a, a, a, a + 4, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN
+    assert bwd(a, a, a, None, a, a, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN            # no lse
+    assert bwd(a, a, a, a, None, a, 1, 577, 1, 0.125, None) == MV_ERR_ALIGN            # no delta workspace
+    # B = 0 is a no-op that launches nothing
+    assert fwd(a, a, a, 0, 577, 1, 0.125, None) == MV_OK
+    assert fwd(a, a, None, 0, 577, 1, 0.125, None) == MV_OK
+    assert q8(a, a, 0, 577, 1, 0.125, 0.05, 128, None) == MV_OK
+    assert bwd(a, a, a, a, a, a, 0, 577, 1, 0.125, None) == MV_OK

@@ -8,9 +8,10 @@ workgroup (256 at width 32).  The battery of tests/test_attention_short.py, with
 
 1. routing: softmax an exact permutation matrix -- which key reaches which query is pinned bit for bit.  A wrong key's block seen
    first leaves garbage in O and l that only the rescale by exp2(m_old - m_new) = 0 removes;
-2. every length against fp64: the ceilings tests/test_attention_long.py, _long_f16.py, _long_f32.py and _dh.py hold these kernels
-   to, the per-element forward and lse bounds re-derived for the online softmax (forward_bound / lse_bound, blocks > 0), and on two
-   harder score distributions a backward bar of 2x the error of an fp64 emulation of the kernels' roundings (emulate, blockwise);
+2. every length against fp64: the ceilings the per-family files hold these kernels to through ops' wrappers (BARS of
+   tests/attention_families.py), the per-element forward and lse bounds re-derived for the online softmax (forward_bound /
+   lse_bound, blocks > 0), and on two harder score distributions a backward bar of 2x the error of an fp64 emulation of the
+   kernels' roundings (emulate, blockwise);
 3. guard zones round every tensor, the workspaces included;
 4. (image, head) independence: the workgroup index mixes query block, image and head;
 5. zero gradient;
@@ -21,6 +22,8 @@ tests/test_attention_short.py::test_routing_builder_gives_an_exact_permutation_s
 import pytest
 import torch
 
+pytest.register_assert_rewrite("attention_families")   # its shared bodies assert: failures show the values
+from attention_families import BARS
 from test_attention_short import (DISTS, MV_ERR_ALIGN, MV_ERR_SHAPE, MV_ERR_UNSUPPORTED, MV_OK, OPERAND, Q8_SCALE, Q8_ZERO, SENTINEL,
                                   TILED_EDGES, TILED_EDGES_DH, Guarded, L, Tight, assert_routed_backward, assert_routed_forward,
                                   emulate, exact_fp64, forward_bound, heads, join_qkv, lse_bound, ops, ptr, random_inputs,  # noqa: F401
@@ -37,12 +40,8 @@ LENGTHS = {"long": TILED_EDGES, "long_f16": TILED_EDGES, "long_f32": TILED_EDGES
 EDGE_CLASS = [17, 65, 129, 257, 385, 513]          # one length per edge class: the harder distributions
 GUARD_N = [1, 17, 65, 129, 257, 321, 513]
 INDEPENDENT_N = {"long": [129, 385], "long_f16": [129, 385], "long_f32": [129, 385], "dh32": [129, 257], "dh128": [129, 385]}
-# whole-tensor L2 ceilings of tests/test_attention_long.py and tests/test_attention_dh.py (bf16), tests/test_attention_long_f16.py
-# (half) and tests/test_attention_long_f32.py (fp32): forward, lse (absolute), each of dq / dk / dv, colsum against the sums of the
-# returned dqkv, colsum against fp64
-BARS = {"bf16": dict(out=1.5e-2, lse=1e-4, grad=3e-2, colsum_own=5e-3, colsum64=3e-2),
-        "half": dict(out=6e-4, lse=2e-5, grad=2e-3, colsum_own=1e-5),
-        "fp32": dict(out=2e-6, lse=2e-5, grad=5e-6)}
+# BARS: the whole-tensor L2 ceilings of each arithmetic, the ones tests/test_attention_long*.py and _dh.py apply: out, lse (absolute), grad
+# (each of dq / dk / dv), colsum_own (against the sums of the returned dqkv), colsum64 (against fp64)
 
 
 def set_lengths(lengths=None):
@@ -203,8 +202,8 @@ def test_routing_is_exact_in_every_tiled_kernel(ops, name, N):
 # ================================================================== 2. every length against fp64
 def part_errors(family, got, want, H, dh):
     """L2 relative error of dq, dk, dv.  A part that is exactly zero in exact arithmetic (dq, dk at N = 1) has no relative error:
-    half and fp32 hold it against the size of the whole gradient as tests/test_attention_long_f16.py and _long_f32.py do; bf16
-    -> None (the caller applies the absolute bound of tests/test_attention_dh.py)."""
+    half and fp32 hold it against the size of the whole gradient as check_against_fp64 of tests/attention_families.py does; bf16
+    -> None (the caller applies that check's absolute bound)."""
     whole, errs = float(want.norm()), []
     for a, b in zip(split_qkv(got, H, dh), split_qkv(want, H, dh)):
         den = float(b.norm())
@@ -284,7 +283,7 @@ def test_every_tiled_edge_against_fp64(ops, name, N, dist):
             for part, e in zip("qkv", part_errors(family, got, want_dqkv, H, dh)):
                 if e is None:
                     # two fp32 sums of the same dh products in different orders (zero_gradient_bound), then one bf16 rounding of dS
-                    # and one of the result: the bound of tests/test_attention_dh.py
+                    # and one of the result: the bound of tests/attention_families.py's bf16 check
                     zb = zero_gradient_bound(qkv, dout, H, dh)[:, :, None, None] * (1 + 2.0 ** -8) ** 2
                     assert bool((split_qkv(got, H, dh)["qkv".index(part)].abs() <= zb).all()), part
                 else:

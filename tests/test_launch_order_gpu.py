@@ -3,7 +3,7 @@ count as a raise for it (mv_launch / mv_grant_lds in csrc/mv_common.h).
 
 A fresh process makes the calls of calls() in order.  Each is the first launch of its kernel in that process and follows a sibling
 instantiation; each must return MV_OK and give the result its own test asks for -- the references, helpers and ceilings are those
-of tests/test_attention_short.py, tests/test_attention_long_f32.py and tests/test_hip_ops.py, imported from there.  The backward
+of tests/test_attention_short.py, tests/attention_families.py and tests/test_hip_ops.py, imported from there.  The backward
 calls take the forward's out and lse from the fp64 reference, so no forward kernel runs between two backward siblings.  The child
 prints one line per call; the parent checks its exit status and counts the lines."""
 import os
@@ -19,7 +19,7 @@ B = H = 1
 def calls():
     """[(label, function)] in launch order"""
     import torch
-    import test_attention_long_f32 as LF
+    import attention_families as AF
     import test_attention_short as S
     import test_hip_ops as G
     from myrtle_vision.hip import ops
@@ -63,9 +63,9 @@ def calls():
             assert torch.equal(r["dqkv"], S.split_of(ops, plain[N], nseg))
 
     def long_f32():
-        qkv, dout = LF.make(B, 65, H, seed=5)
-        LF.check_against_fp64(ops, qkv, dout, B, 65, H, ops.attention_fwd_long_f32,
-                              lambda *a: ops.attention_fwd_long_f32(*a, lse=False), ops.attention_bwd_long_f32, vs_materialised=False)
+        fam = AF.FAMILIES["fp32"]
+        qkv, dout = AF.make(fam, ops, B, 65, H, seed=5)
+        AF.check_against_fp64(fam, ops, qkv, dout, B, 65, H, long=True)
 
     def gemm_nt(variant):
         check(lib().mv_gemm_force_variant(variant, 0), "force_variant")
