@@ -470,6 +470,40 @@ int mv_seg_ce_fwd(const float* small, const int64_t* labels, float* lse, uint8_t
 int mv_seg_ce_bwd(const float* small, const int64_t* labels, const float* lse, const float* stats, void* dsmall,
                   int ds_dtype, int ld_ds, float grad_scale, int B, int C, int h, int w, int H, int W, mv_stream_t stream);
 
+/* ---- fused segmentation tail with a training recipe (csrc/seg_loss.hip): class weights, label smoothing, soft Dice ----
+ * An extension: the reference trains segmentation on the plain mean cross entropy only (segmentation/train.py:188), which stays
+ * with mv_seg_ce_* above, untouched.  With z = the bilinearly upsampled logits (the expressions of mv_seg_ce_*), p = softmax(z),
+ * y the label, w_c = class_weight[c] (NULL: ones; a DEVICE array, >= 0), eps = label_smoothing, lam = dice_weight, s = dice_smooth,
+ * "valid" = 0 <= y < C (y == -100 is ignored: no loss, no gradient, not counted; any other label outside [0, C) makes the loss NaN,
+ * is never used as an index and gives no gradient):
+ *   CE   = [(1-eps) sum_valid w_y (lse - z_y) + (eps/C) sum_valid sum_c w_c (lse - z_c)] / W,   W = sum_valid w_y
+ *          (= torch.nn.functional.cross_entropy(z, y, weight=w, label_smoothing=eps); NaN when W == 0)
+ *   Dice = 1 - (1/C) sum_c (2 I_c + s) / (P_c + N_c + s),  I_c = sum_valid p_c [y=c], P_c = sum_valid p_c, N_c = sum_valid [y=c]
+ *          (over the whole batch; 0 when lam == 0)
+ *   loss = CE + lam Dice
+ * fwd: small fp32 [B, h*w, C], labels int64 [B, H, W]; lse fp32 [B,H,W] and pred uint8 [B,H,W] are bitwise those of mv_seg_ce_fwd;
+ *      partials fp32 [mv_seg_loss_partials(B,C,H,W)] scratch (0 for an empty batch); stats fp32 [8]: [0] loss, [1] pixel accuracy
+ *      over all pixels, [2] counted labels, [3] out-of-range labels, [4] CE, [5] Dice, [6] W, [7] 0; coef fp32 [2*C] = (a_c | b_c),
+ *      a_c = -(2/C)/U_c, b_c = (1/C)(2 I_c + s)/U_c^2, U_c = P_c + N_c + s (zeros when lam == 0); areas int64 [3*C] or NULL =
+ *      (intersect_c | pred_c | label_c) with the semantics of utils/miou.intersect_and_union: pred_c over all pixels, intersect_c
+ *      where pred == label == c, labels outside [0, C) dropped.  Bitwise reproducible: every float sum has a fixed order (no float
+ *      atomics), counts are integers throughout (int64 totals).  Never synchronises, no memset: graph-capture safe.
+ *      B == 0: a kernel clears stats and areas, MV_OK.
+ * bwd: lse, stats, coef = the forward's (coef may be NULL when dice_weight == 0); dsmall (element type ds_elem = MV_F32 | MV_BF16,
+ *      [B*h*w, ld_ds], columns [C, ld_ds) zeroed) = d(loss)/d(small) * grad_scale, gather form, deterministic; per valid pixel
+ *        dz_c = [p_c ((1-eps) w_y + (eps/C) sum_k w_k) - (1-eps) w_y [y=c] - (eps/C) w_c] / W + lam p_c (g_c - sum_k p_k g_k),
+ *        g_c = a_c [y=c] + b_c;   all zero when W == 0.
+ * MV_ERR_SHAPE: a non-positive dimension, B < 0, B > 65535, ld_ds < C.  MV_ERR_UNSUPPORTED: C > 32; the per-image map (plus, in
+ * bwd, W*C column sums) beyond 64 KB of LDS; label_smoothing outside [0, 1); dice_weight < 0; dice_weight > 0 with
+ * dice_smooth <= 0; ds_elem neither MV_F32 nor MV_BF16.  All answered before any launch. */
+long mv_seg_loss_partials(int B, int C, int H, int W);
+int mv_seg_loss_fwd(const float* small, const int64_t* labels, const float* class_weight, float label_smoothing,
+                    float dice_weight, float dice_smooth, float* lse, uint8_t* pred, float* partials, float* stats, float* coef,
+                    int64_t* areas, int B, int C, int h, int w, int H, int W, mv_stream_t stream);
+int mv_seg_loss_bwd(const float* small, const int64_t* labels, const float* class_weight, float label_smoothing,
+                    float dice_weight, const float* lse, const float* stats, const float* coef, void* dsmall, int ds_elem,
+                    int ld_ds, float grad_scale, int B, int C, int h, int w, int H, int W, mv_stream_t stream);
+
 /* ---- YOLOS detection tail (csrc/detection.hip).  Everything is fp32 in every precision; Q = num_det_tokens queries per image,
  * C1 = num_classes + 1 (the last class is "no object"), boxes are (cx, cy, w, h) in [0, 1]. ----
  * decoder: vit.py:376-396 DetectionDecoder.forward -- x[:, -Q:, :] -> class_embed, bbox_embed + sigmoid -- in one pass over the

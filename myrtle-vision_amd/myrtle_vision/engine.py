@@ -258,6 +258,30 @@ def _train_criterion(task, train_config):
     return SoftTargetCrossEntropy(smoothing, return_argmax=True), mixer
 
 
+_SEG_LOSS_KEYS = ("class_weights", "label_smoothing", "dice_weight", "dice_smooth")
+
+
+def _seg_loss_spec(task, train_config, num_classes=None):
+    """-> ``SegLoss`` from the optional ``train_config["seg_loss"]`` object (keys ``class_weights``: a list of ``number_of_classes``
+    floats or null, ``label_smoothing``, ``dice_weight``, ``dice_smooth``), or None without the key: an extension, the reference
+    trains segmentation on the plain mean cross entropy.  Segmentation only -- the key on another task is an error -- and training
+    only: validation and testing keep the plain criterion, so ``val_loss`` stays comparable between recipes."""
+    if "seg_loss" not in train_config:
+        return None
+    if task != "segmentation":
+        raise ValueError(f"train_config key 'seg_loss' is the segmentation recipe (class weights / label smoothing / Dice on the "
+                         f"fused tail); task={task!r} does not take it")
+    cfg = train_config["seg_loss"]
+    if not isinstance(cfg, dict) or set(cfg) - set(_SEG_LOSS_KEYS):
+        raise ValueError(f"train_config['seg_loss'] must be an object with keys among {_SEG_LOSS_KEYS}, got {cfg!r}")
+    from myrtle_vision.hip.functional import SegLoss
+    spec = SegLoss(class_weights=cfg.get("class_weights"), label_smoothing=cfg.get("label_smoothing", 0.0),
+                   dice_weight=cfg.get("dice_weight", 0.0), dice_smooth=cfg.get("dice_smooth", 1.0))
+    if num_classes is not None:
+        spec.check_classes(num_classes)
+    return spec
+
+
 @torch.no_grad()
 def validation(val_loader, device, criterion, vit, task, num_classes):
     total_loss, total_acc, n = 0.0, 0.0, max(len(val_loader), 1)
@@ -281,10 +305,12 @@ def validation(val_loader, device, criterion, vit, task, num_classes):
 
 def train_worker(rank, num_gpus, config, task="classification"):
     if task == "detection":
+        _seg_loss_spec(task, config["train_config"])           # the segmentation recipe key on this task: an error before any work
         return _train_detection(rank, num_gpus, config)
     train_config, dist_config, vit_config = config["train_config"], config["dist_config"], config["vit_config"]
     data_config = parse_config(config["data_config_path"])
     train_criterion, mixer = _train_criterion(task, train_config)      # first: a recipe key on the wrong task fails before any work
+    seg_spec = _seg_loss_spec(task, train_config, data_config["number_of_classes"])
     if not torch.cuda.is_available():
         raise RuntimeError("training needs an MI355X: the myrtle_vision HIP path has no CPU fallback")
     device = torch.device("cuda", rank)
@@ -352,6 +378,7 @@ def train_worker(rank, num_gpus, config, task="classification"):
     num_classes = data_config["number_of_classes"]
     for epoch in range(epoch_offset, train_config["epochs"]):
         epoch_loss = epoch_acc = 0.0
+        train_miou = MIoU(num_classes, device) if seg_spec is not None else None
         if sampler is not None:
             sampler.set_epoch(epoch)
         for imgs, labels in train_loader:
@@ -367,7 +394,10 @@ def train_worker(rank, num_gpus, config, task="classification"):
             if n_accum == 0:
                 optimizer.zero_grad()
             reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
-            if _fused_seg_tail(task, criterion):
+            if seg_spec is not None:                             # class weights / smoothing / Dice: the fused tail or an error
+                loss, acc_t, _, areas = vit.segmentation_loss(imgs, labels, loss=seg_spec, return_areas=True)
+                train_miou.add_areas(areas)                      # counted by the loss kernel: no second pass, no synchronisation
+            elif _fused_seg_tail(task, criterion):
                 loss, acc_t, _ = vit.segmentation_loss(imgs, labels)
             elif train_criterion is criterion:
                 outputs = vit(imgs)
@@ -397,6 +427,8 @@ def train_worker(rank, num_gpus, config, task="classification"):
         lr_scheduler.step(epoch)
         if rank == 0:
             extra = f" - val_miou: {last_val[2]:.4f}" if last_val[2] is not None else ""
+            if train_miou is not None:                           # this rank's batches of the epoch
+                extra = f" - train_miou: {train_miou.get_miou():.4f}" + extra
             print(f"Epoch : {epoch + 1} - loss : {epoch_loss:.4f} - acc: {epoch_acc:.4f} - "
                   f"val_loss : {last_val[0]:.4f} - val_acc: {last_val[1]:.4f}{extra}\n")
     if scalars is not None:

@@ -931,8 +931,98 @@ class _SegHeadLoss(Function):
         return (*_seg_small_bwd(saved, ctx.small, (B, T, D, C), dl, ld), None, None, None, None)
 
 
-def seg_head_loss(x, g, b, w, bias, labels, grid, size, prec):
-    return _SegHeadLoss.apply(x, g, b, w, bias, labels, grid, size, prec)
+class SegLoss:
+    """The training loss of the fused segmentation tail, as a validated, immutable specification (mv_seg_loss_*):
+
+        loss = cross_entropy(z, y, weight=class_weights, label_smoothing=label_smoothing) + dice_weight * Dice
+
+    with the soft Dice of include/myrtle_vision_hip.h over the whole batch (``dice_smooth`` in numerator and denominator).  Not a
+    callable criterion: the logits it applies to are never written, so it exists on the fused tail only
+    (``ViT.segmentation_loss(img, labels, loss=spec)``).  The weights are uploaded once per device, when first used there."""
+    __slots__ = ("class_weights", "label_smoothing", "dice_weight", "dice_smooth", "_on")
+
+    def __init__(self, class_weights=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0):
+        if class_weights is not None:
+            class_weights = tuple(float(v) for v in class_weights)
+            if not class_weights:
+                raise ValueError("SegLoss: class_weights is empty")
+            if any(not (v >= 0.0) or v == float("inf") for v in class_weights):
+                raise ValueError(f"SegLoss: class_weights must be finite and >= 0, got {class_weights}")
+        label_smoothing, dice_weight, dice_smooth = float(label_smoothing), float(dice_weight), float(dice_smooth)
+        if not (0.0 <= label_smoothing < 1.0):
+            raise ValueError(f"SegLoss: label_smoothing must lie in [0, 1), got {label_smoothing}")
+        if not (dice_weight >= 0.0) or dice_weight == float("inf"):
+            raise ValueError(f"SegLoss: dice_weight must be finite and >= 0, got {dice_weight}")
+        if dice_weight > 0.0 and not (dice_smooth > 0.0 and dice_smooth != float("inf")):
+            raise ValueError(f"SegLoss: dice_smooth must be finite and > 0 when dice_weight > 0, got {dice_smooth}")
+        for k, v in (("class_weights", class_weights), ("label_smoothing", label_smoothing), ("dice_weight", dice_weight),
+                     ("dice_smooth", dice_smooth), ("_on", {})):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("SegLoss is immutable")
+
+    def __repr__(self):
+        return (f"SegLoss(class_weights={self.class_weights}, label_smoothing={self.label_smoothing}, "
+                f"dice_weight={self.dice_weight}, dice_smooth={self.dice_smooth})")
+
+    def check_classes(self, C):
+        if self.class_weights is not None and len(self.class_weights) != C:
+            raise ValueError(f"SegLoss: {len(self.class_weights)} class_weights for {C} classes")
+
+    def weight_on(self, device):
+        """fp32 [C] on ``device`` (uploaded on first use there), or None."""
+        if self.class_weights is None:
+            return None
+        device = torch.device(device)
+        t = self._on.get(device)
+        if t is None:
+            t = self._on[device] = torch.tensor(self.class_weights, dtype=torch.float32, device=device)
+        return t
+
+
+class _SegHeadLossRecipe(Function):
+    """_SegHeadLoss with a SegLoss (mv_seg_loss_*) -> (loss, pixel accuracy, pred uint8 [B,S,S], areas int64 [3, C])."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, x, g, b, w, bias, labels, grid, size, spec, prec):           # prec last: _fwd reads it there
+        B, T, D = x.shape
+        C = w.shape[0]
+        small, saved, ctx.small = _seg_small_fwd(x, g, b, w, bias, prec)
+        cw = spec.weight_on(small.device)
+        kw = dict(class_weight=cw, label_smoothing=spec.label_smoothing, dice_weight=spec.dice_weight)
+        stats, lse, pred, coef, areas, labels = ops.seg_loss_fwd(small, labels, B, C, grid, grid, size, size,
+                                                                 dice_smooth=spec.dice_smooth, **kw)
+        adt = ops.act_dtype(prec)
+        ctx.needs = any(ctx.needs_input_grad[:5])
+        if ctx.needs:
+            ld = ops.pad8(C) if adt == torch.bfloat16 else C
+            # the gradient of the loss, produced now (labels and lse are hot), scaled by the incoming g in backward
+            dl = ops.seg_loss_bwd(small, labels, lse, stats, coef, B, C, grid, grid, size, size, grad_dtype=adt, ld=ld, **kw)
+            ctx.save_for_backward(dl, *saved)
+            ctx.dims = (B, T, D, C, ld)
+        ctx.mark_non_differentiable(pred, areas)
+        return stats[0], stats[1].detach(), pred, areas
+
+    @staticmethod
+    @_scoped
+    def backward(ctx, gloss, _gacc, _gpred, _gareas):
+        dl, *saved = ctx.saved_tensors
+        B, T, D, C, ld = ctx.dims
+        dl = dl * gloss.to(dl.dtype)                                          # [B*h*w, ld]: tiny
+        return (*_seg_small_bwd(saved, ctx.small, (B, T, D, C), dl, ld), None, None, None, None, None)
+
+
+def seg_head_loss(x, g, b, w, bias, labels, grid, size, prec, loss=None):
+    """``loss=None``: the plain mean cross entropy (mv_seg_ce_*) -> (loss, accuracy, pred).  A ``SegLoss``: mv_seg_loss_* ->
+    (loss, accuracy, pred, areas int64 [3, C])."""
+    if loss is None:
+        return _SegHeadLoss.apply(x, g, b, w, bias, labels, grid, size, prec)
+    if not isinstance(loss, SegLoss):
+        raise TypeError(f"seg_head_loss: loss must be a SegLoss or None, got {type(loss).__name__}")
+    loss.check_classes(w.shape[0])
+    return _SegHeadLossRecipe.apply(x, g, b, w, bias, labels, grid, size, loss, prec)
 
 
 def seg_head(x, g, b, w, bias, grid, size, prec):

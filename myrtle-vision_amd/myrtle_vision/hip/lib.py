@@ -102,6 +102,9 @@ SIGNATURES = {
     "mv_seg_ce_partials": ("iii", _L),
     "mv_seg_ce_fwd": ("pppppp" "iiiiii" "p", _I),
     "mv_seg_ce_bwd": ("ppppp" "ii" "f" "iiiiii" "p", _I),
+    "mv_seg_loss_partials": ("iiii", _L),
+    "mv_seg_loss_fwd": ("ppp" "fff" "pppppp" "iiiiii" "p", _I),
+    "mv_seg_loss_bwd": ("ppp" "ff" "pppp" "ii" "f" "iiiiii" "p", _I),
     "mv_det_heads_fwd": ("ppppppp" "iiiii" "p", _I),
     "mv_det_heads_bwd_workspace_bytes": ("iiii", _Z),
     "mv_det_heads_bwd": ("ppppppppppp" "pz" "iiiii" "p", _I),

@@ -1562,6 +1562,54 @@ def seg_ce_bwd(small, labels, lse, B, C, h, w, H, W, *, grad_dtype=torch.float32
     return ds
 
 
+SEG_LOSS_MAX_CLASSES = 32
+SEG_LOSS_FWD_EXTRA, SEG_LOSS_BWD_EXTRA = 400, 128          # LDS words behind the map: csrc/seg_loss.hip SL_FWD_EXTRA / SL_BWD_EXTRA
+
+
+def seg_loss_supported(C, h, w, W):
+    """Shapes the fused segmentation tail WITH a recipe covers (mv_seg_loss_* return MV_ERR_UNSUPPORTED outside them)."""
+    return (C <= SEG_LOSS_MAX_CLASSES and (h * w * C + SEG_LOSS_FWD_EXTRA) * 4 <= SEG_CE_LDS_LIMIT
+            and (h * w * C + W * C + SEG_LOSS_BWD_EXTRA) * 4 <= SEG_CE_LDS_LIMIT)
+
+
+def seg_loss_fwd(small, labels, B, C, h, w, H, W, *, class_weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0,
+                 areas=True):
+    """small fp32 [B*h*w, C], labels int64 [B,H,W], class_weight fp32 [C] on the device or None (ones) ->
+    (stats [8] = loss, pixel accuracy, counted labels, bad labels, CE, Dice, sum of w_y, 0; lse [B,H,W]; pred u8 [B,H,W];
+    coef [2, C] = (a_c, b_c) of the Dice gradient; areas int64 [3, C] = (intersect, pred, label) or None; labels as read)."""
+    require_cuda(small, labels)
+    labels = labels.contiguous()
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    if class_weight is not None:
+        require_cuda(class_weight)
+        if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (C,) or not class_weight.is_contiguous():
+            raise RuntimeError(f"seg_loss_fwd: class_weight must be a contiguous fp32 [{C}] tensor")
+    dev = small.device
+    lse = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    pred = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    partials = torch.empty(max(lib().mv_seg_loss_partials(B, C, H, W), 4), dtype=torch.float32, device=dev)
+    stats = torch.empty(8, dtype=torch.float32, device=dev)
+    coef = torch.empty(2, C, dtype=torch.float32, device=dev)
+    ar = torch.empty(3, C, dtype=torch.int64, device=dev) if areas else None
+    check(lib().mv_seg_loss_fwd(_p(small), _p(labels), _p(class_weight), label_smoothing, dice_weight, dice_smooth, _p(lse), _p(pred),
+                                _p(partials), _p(stats), _p(coef), _p(ar), B, C, h, w, H, W, _s()),
+          "seg_loss_fwd", B=B, C=C, h=h, w=w, H=H, W=W, label_smoothing=label_smoothing, dice_weight=dice_weight,
+          dice_smooth=dice_smooth)
+    return stats, lse, pred, coef, ar, labels
+
+
+def seg_loss_bwd(small, labels, lse, stats, coef, B, C, h, w, H, W, *, class_weight=None, label_smoothing=0.0, dice_weight=0.0,
+                 grad_dtype=torch.float32, ld=None, grad_scale=1.0):
+    """``stats`` and ``coef``: the forward's.  -> d(loss)/d(small) * grad_scale, ``grad_dtype`` [B*h*w, ld]."""
+    ld = C if ld is None else ld
+    ds = torch.empty(B * h * w, ld, dtype=grad_dtype, device=small.device)
+    check(lib().mv_seg_loss_bwd(_p(small), _p(labels), _p(class_weight), label_smoothing, dice_weight, _p(lse), _p(stats), _p(coef),
+                                _p(ds), _DT[grad_dtype], ld, grad_scale, B, C, h, w, H, W, _s()),
+          "seg_loss_bwd", B=B, C=C, h=h, w=w, H=H, W=W, ld=ld, label_smoothing=label_smoothing, dice_weight=dice_weight)
+    return ds
+
+
 # ------------------------------------------------------------------------------------------------------------
 # YOLOS detection tail (csrc/detection.hip): fp32 in every precision
 # ------------------------------------------------------------------------------------------------------------

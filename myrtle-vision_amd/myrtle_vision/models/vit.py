@@ -506,13 +506,26 @@ class ViT(nn.Module):
             output = self.dequant_output(output)
         return output
 
-    def segmentation_loss(self, img: torch.Tensor, labels: torch.Tensor):
+    def segmentation_loss(self, img: torch.Tensor, labels: torch.Tensor, loss=None, return_areas: bool = False):
         """Extension: what segmentation/train.py:260-265 computes from ``vit(img)`` --
         ``CrossEntropyLoss()(outputs, labels)``, ``outputs.argmax(dim=1)`` and the pixel accuracy -- in one fused tail
         that never writes the [B, C, H, W] logits.  -> (loss, accuracy, pred uint8 [B, H, W]).  Falls back to the
-        separate HIP kernels (same numbers, more HBM traffic) for shapes the fused kernels do not cover."""
+        separate HIP kernels (same numbers, more HBM traffic) for shapes the fused kernels do not cover.
+
+        ``loss``: a ``hip.functional.SegLoss`` (class weights, label smoothing, Dice) replaces the plain mean cross entropy.  It
+        exists on the fused tail only: where that does not apply (quantiser stubs in the decoder, more than 32 classes, a map too
+        large for LDS) this raises a ValueError naming the limit; nothing falls back to another formula.  ``return_areas=True``
+        adds a fourth value, the int64 [3, C] (intersect | pred | label) areas of ``utils.miou.MIoU.add_areas``, counted by the
+        same kernel (without ``loss`` the plain cross entropy is then computed as ``SegLoss()``, every option off)."""
         if not isinstance(self.decoder, SegmentationDecoder):
             raise ValueError("segmentation_loss needs decoder='segmentation'")
+        if loss is not None or return_areas:
+            self.decoder.require_recipe_tail(labels)            # before any device work
+            with ops.segments(ops.prec_segments(self.precision)):
+                x = self._backbone(img)
+                with self.cm_mlp_head:
+                    out = self.decoder.loss(x, labels, loss=loss if loss is not None else F.SegLoss())
+            return out if return_areas else out[:3]
         with ops.segments(ops.prec_segments(self.precision)):
             x = self._backbone(img)
             with self.cm_mlp_head:
@@ -621,14 +634,33 @@ class SegmentationDecoder(nn.Module):
                 and tuple(labels.shape[1:]) == (self.image_size, self.image_size)
                 and ops.seg_ce_supported(self.linear.out_features, g, g, self.image_size))
 
-    def loss(self, x: torch.Tensor, labels: torch.Tensor):
-        """Fused decoder + mean cross entropy + argmax: (loss, pixel accuracy, pred uint8 [B, S, S])."""
+    def require_recipe_tail(self, labels) -> None:
+        """ValueError naming the limit where the fused tail with a ``SegLoss`` (mv_seg_loss_*) does not apply."""
+        g, C = self.image_size_in_patches, self.linear.out_features if _plain(self.linear, Linear) else None
+        if not (_plain(self.norm, LayerNorm) and _plain(self.linear, Linear)) or self._forward_hooks or self.upsample._forward_hooks:
+            raise ValueError("a SegLoss needs the fused segmentation tail: the decoder's norm / linear are wrapped (quantiser "
+                             "stubs) or hooked, so its logits are produced module by module")
+        if not isinstance(self.image_size, int) or tuple(labels.shape[1:]) != (self.image_size, self.image_size):
+            raise ValueError(f"a SegLoss needs the fused segmentation tail: labels {tuple(labels.shape)} are not "
+                             f"[B, {self.image_size}, {self.image_size}]")
+        if C > ops.SEG_LOSS_MAX_CLASSES:
+            raise ValueError(f"a SegLoss needs the fused segmentation tail: {C} classes exceed its limit of "
+                             f"{ops.SEG_LOSS_MAX_CLASSES}")
+        if not ops.seg_loss_supported(C, g, g, self.image_size):
+            raise ValueError(f"a SegLoss needs the fused segmentation tail: a {g}x{g}x{C} map with {self.image_size} output "
+                             f"columns exceeds its {ops.SEG_CE_LDS_LIMIT // 1024} KB of LDS")
+
+    def loss(self, x: torch.Tensor, labels: torch.Tensor, loss=None):
+        """Fused decoder + mean cross entropy + argmax: (loss, pixel accuracy, pred uint8 [B, S, S]); with ``loss`` (a
+        ``SegLoss``) that loss instead, and a fourth value: the int64 [3, C] (intersect | pred | label) areas."""
         g = self.image_size_in_patches
         if x.shape[1] - 1 != g * g:
             raise ValueError(f"expected {g * g} patch tokens for image_size {self.image_size}, got {x.shape[1] - 1}")
+        if loss is not None:
+            self.require_recipe_tail(labels)
         ops.require_cuda(x, labels)
         return F.seg_head_loss(x.float(), self.norm.weight, self.norm.bias, self.linear.weight, self.linear.bias, labels,
-                               g, self.image_size, self.norm.precision)
+                               g, self.image_size, self.norm.precision, loss=loss)
 
 
 # ---- reference vit.py:376-396 -------------------------------------------------------------------------------

@@ -28,6 +28,14 @@ class MIoU:
         self.total_area_intersect += i.to(self.total_area_intersect.device)
         self.total_area_union += u.to(self.total_area_union.device)
 
+    def add_areas(self, areas):
+        """``areas``: int64 [3, C] = (intersect | pred | label) per class, as the fused segmentation tail counts them
+        (``ViT.segmentation_loss(..., return_areas=True)``): the totals ``add_img(pred, labels)`` adds, without a second trip over
+        the pixels and without a host synchronisation."""
+        a = areas.reshape(3, self.num_classes).to(self.total_area_intersect.device).double()
+        self.total_area_intersect += a[0]
+        self.total_area_union += a[1] + a[2] - a[0]
+
     def get_per_class_iou(self):
         return self.total_area_intersect / self.total_area_union
 
