@@ -73,7 +73,8 @@ const char* mv_error_string(int code);
 size_t mv_gemm_tn_workspace_bytes(int M, int N, int Kc);
 /* Tuning / test hook (no reference counterpart): force a kernel variant for the following mv_gemm_nt_bf16 (0 auto | 128 | 2564 ring |
  * 2568 8-phase | 25680 8-phase without the half-item tail | 3000 / 3002 automatic dispatch with the 8-phase kernel's column bands
- * off / on | 3100 / 3102 the same with the 8-phase kernel forced) and mv_gemm_tn_bf16 (0 auto | 128 | 256 ring) calls of this
+ * off / on | 3100 / 3102 the same with the 8-phase kernel forced) and mv_gemm_tn_bf16 (0 auto | 128 | 256 ring; 1000 more, i.e.
+ * 1000 | 1128 | 1256: the same, and mv_gemm_tn_bf16_group runs its items one by one) calls of this
  * process; a forced variant that cannot run a shape (alignment of K) falls back to the automatic choice.  Results are identical up
  * to fp32 summation order (bands on / off: bit for bit). */
 int mv_gemm_force_variant(int nt_variant, int tn_variant);
@@ -126,6 +127,25 @@ int mv_gemm_nt_bf16_scaled(const void* A, int lda, const void* B, int ldb, void*
  * reduced deterministically.  colsum (optional, fp32 [M]) (+)= column sums of A = bias gradient. */
 int mv_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int Kc,
                     int accumulate, float* colsum, float* workspace, size_t workspace_bytes, mv_stream_t stream);
+/* Up to 4 weight gradients over the SAME Kc token rows (the to_out and to_qkv products of one attention block) in one launch:
+ * C_i[M_i, N_i] = A_i[Kc, M_i]^T . B_i[Kc, N_i], no accumulate, no colsum.  `items` is a HOST array, read before the call returns.
+ * The split count is chosen for the items' tiles together and is the same for all of them; one reduce sums every item's slabs
+ * in split order (deterministic).  When Kc is not a multiple of 32, an item alone would not take the 256-tile kernel, or the TN
+ * force code is 1000 + family, the items run one after another exactly as mv_gemm_tn_bf16 calls (same bits as those).  A
+ * one-item group computes what mv_gemm_tn_bf16 computes, bit for bit. */
+typedef struct mv_tn_item {
+  const void* A;
+  int lda;
+  const void* B;
+  int ldb;
+  float* C;
+  int ldc;
+  int M;
+  int N;
+} mv_tn_item;
+size_t mv_gemm_tn_group_workspace_bytes(const mv_tn_item* items, int n_items, int Kc);
+int mv_gemm_tn_bf16_group(const mv_tn_item* items, int n_items, int Kc, float* workspace, size_t workspace_bytes,
+                          mv_stream_t stream);
 
 /* ---- generic fp32 contraction (exact-parity mode, odd shapes, materialised attention) ----
  * C[b1,b2][m,n] = sum_k A[b1,b2][m,k] * B[b1,b2][k,n] with arbitrary element strides; same epilogues

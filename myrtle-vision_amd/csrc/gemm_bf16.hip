@@ -1515,17 +1515,44 @@ struct TnSeg {
   int tiles;
   int a[6], b[6];
 };
-template <int S, bool SEG = false>
+// GROUP (mv_gemm_tn_bf16_group): several products over ONE contraction range share the launch.  Their tiles are concatenated
+// (item i owns tiles [tile0[i], tile0[i + 1]) of every split) and tiles_mn counts all of them, so the unit index
+// split * tiles_mn + tile keeps one split per XCD exactly as a single product does.  A workgroup looks its item up once, here at
+// entry (uniform: scalar selects from the table in the kernel arguments), and runs the unchanged loop on that item's operands.
+// A, B, C, M, N, the leading dimensions and tiles_n of the launch are ignored; ldc too: every item brings its own.
+constexpr int TN_GROUP_MAX = 4;
+struct TnGroup {
+  const bf16_t* A[TN_GROUP_MAX];
+  const bf16_t* B[TN_GROUP_MAX];
+  float* out[TN_GROUP_MAX];            // slab 0 of the item (or its C when the plan has one split)
+  int lda[TN_GROUP_MAX], ldb[TN_GROUP_MAX], ld_out[TN_GROUP_MAX], M[TN_GROUP_MAX], N[TN_GROUP_MAX], tiles_n[TN_GROUP_MAX];
+  int tile0[TN_GROUP_MAX];             // unused entries: INT_MAX
+};
+template <int S, bool SEG = false, bool GROUP = false>
 __global__ __launch_bounds__(512, 2) void gemm_tn_ring_kernel(const bf16_t* __restrict__ A, int lda,
                                                               const bf16_t* __restrict__ B, int ldb, float* __restrict__ C,
                                                               long ldc, long slab_stride, int M, int N, int Kc, int tiles_n,
-                                                              int tiles_mn, int steps_per_split, TnSeg seg) {
+                                                              int tiles_mn, int steps_per_split,
+                                                              std::conditional_t<GROUP, TnGroup, TnSeg> seg) {
+  static_assert(!(SEG && GROUP), "a grouped launch has no segment table");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int t_all = xcd_remap(blockIdx.x, gridDim.x);
   const int split = t_all / tiles_mn;
-  const int t = t_all - split * tiles_mn;
+  int t = t_all - split * tiles_mn;
+  if constexpr (GROUP) {
+    int first = 0;
+#pragma unroll
+    for (int i = 0; i < TN_GROUP_MAX; ++i)
+      if (t >= seg.tile0[i]) {
+        A = seg.A[i], B = seg.B[i], C = seg.out[i];
+        lda = seg.lda[i], ldb = seg.ldb[i], ldc = seg.ld_out[i];
+        M = seg.M[i], N = seg.N[i], tiles_n = seg.tiles_n[i];
+        first = seg.tile0[i];
+      }
+    t -= first;
+  }
   const int m0 = (t / tiles_n) * BM2, n0 = (t % tiles_n) * BN2;
   const int nk_total = Kc / BKR;
   const int kt0 = split * steps_per_split;
@@ -1552,8 +1579,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_ring_kernel(const bf16_t* __re
   const mv_srd_t rsA = mv_make_srd(A, 0xFFFFFFFCu), rsB = mv_make_srd(B, 0xFFFFFFFCu);   // whole-operand extents (< 4 GiB: checked by the host)
   const long astep = (long)BKR * lda, bstep = (long)BKR * ldb;
   // SEG: running (segment, stage-in-segment) of the NEXT stage to issue; stages are issued strictly in order
-  int seg_s = SEG ? kt0 / seg.tiles : 0, seg_r = SEG ? kt0 - seg_s * seg.tiles : 0;
-  long seg_ao = SEG ? seg.a[seg_s] + seg_r * astep : 0, seg_bo = SEG ? seg.b[seg_s] + seg_r * bstep : 0;
+  int seg_s = 0, seg_r = 0;
+  long seg_ao = 0, seg_bo = 0;
+  if constexpr (SEG) {
+    seg_s = kt0 / seg.tiles, seg_r = kt0 - seg_s * seg.tiles;
+    seg_ao = seg.a[seg_s] + seg_r * astep, seg_bo = seg.b[seg_s] + seg_r * bstep;
+  }
 #define TNR_ISSUE(slot_, kt_)                                                          \
   {                                                                                    \
     char* la_ = wave_lds + (slot_) * RSTAGE_BYTES;                                     \
@@ -1656,14 +1687,15 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_ring_kernel(const bf16_t* __re
 }
 
 // C[m][n] = (accumulate ? C : 0) + sum_s slab[s][m][n]   (fixed order: deterministic)
-__global__ void splitk_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int S, float* C, int ldc, int M,
-                                     int N, int accumulate) {
+// block `bid` of the `nblocks` that share this product (the whole grid, or one item's share of a grouped launch)
+__device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ slabs, long slab_stride, int S, float* C, int ldc,
+                                                   int M, int N, int accumulate, int bid, int nblocks) {
   const long total = (long)M * N;
   if (ldc == N && (total & 3) == 0 && (slab_stride & 3) == 0) {
     // dense destination (every dW slot of the gradient arena): 16-byte accesses, no index division -- the scalar form below
     // ran at 2.8 TB/s (15 us per launch, 49 launches per ViT-B step); same summation order per element, same bits
     const long total4 = total >> 2;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+    for (long i = (long)bid * blockDim.x + threadIdx.x; i < total4; i += (long)nblocks * blockDim.x) {
       float4 s = reinterpret_cast<const float4*>(slabs)[i];
       s.x += 0.f; s.y += 0.f; s.z += 0.f; s.w += 0.f;     // the scalar form starts from 0.f + slab 0: -0.0 becomes +0.0 there
       for (int k = 1; k < S; ++k) {
@@ -1679,13 +1711,40 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slabs, long slab_
     }
     return;
   }
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+  for (long idx = (long)bid * blockDim.x + threadIdx.x; idx < total; idx += (long)nblocks * blockDim.x) {
     const int m = (int)(idx / N), n = (int)(idx - (long)m * N);
     float s = 0.f;
     for (int k = 0; k < S; ++k) s += slabs[(long)k * slab_stride + idx];
     float* c = C + (long)m * ldc + n;
     *c = accumulate ? (*c + s) : s;
   }
+}
+
+__global__ void splitk_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int S, float* C, int ldc, int M,
+                                     int N, int accumulate) {
+  splitk_reduce_body(slabs, slab_stride, S, C, ldc, M, N, accumulate, blockIdx.x, gridDim.x);
+}
+
+// The same for the items of a grouped launch: every slab holds the items' [M][N] blocks one after another (item i at `off[i]`
+// floats, a multiple of 4), blocks [block0[i], block0[i + 1]) of the grid sum item i into its own C with its own ldc.
+struct TnReduceGroup {
+  float* C[TN_GROUP_MAX];
+  long off[TN_GROUP_MAX];
+  int ldc[TN_GROUP_MAX], M[TN_GROUP_MAX], N[TN_GROUP_MAX];
+  int block0[TN_GROUP_MAX + 1];        // unused entries: the grid size
+};
+__global__ void splitk_reduce_group_kernel(const float* __restrict__ slabs, long slab_stride, int S, TnReduceGroup grp) {
+  float* C = grp.C[0];
+  long off = grp.off[0];
+  int ldc = grp.ldc[0], M = grp.M[0], N = grp.N[0], b0 = 0, b1 = grp.block0[1];
+#pragma unroll
+  for (int i = 1; i < TN_GROUP_MAX; ++i)
+    if ((int)blockIdx.x >= grp.block0[i]) {
+      C = grp.C[i], off = grp.off[i], ldc = grp.ldc[i], M = grp.M[i], N = grp.N[i];
+      b0 = grp.block0[i], b1 = grp.block0[i + 1];
+    }
+  if (b1 <= b0) return;
+  splitk_reduce_body(slabs + off, slab_stride, S, C, ldc, M, N, 0, blockIdx.x - b0, b1 - b0);
 }
 
 // ---- column sums (bias gradient): partial[y][c] = sum over this block's rows of x[r][c] -------------
@@ -1758,11 +1817,8 @@ TnPlan tn_plan(int M, int N, int Kc) {
 }
 
 // 256x256 ring variant: one workgroup per CU, so the split count is chosen to land just under ONE round of the 256 CUs
-TnPlan tn_plan256(int M, int N, int Kc) {
-  TnPlan pl;
-  pl.tiles_m = mv_cdiv(M, BM2);
-  pl.tiles_n = mv_cdiv(N, BN2);
-  const int tiles = pl.tiles_m * pl.tiles_n;
+// `tiles` counts the output tiles of the launch: one product's, or all items' of a grouped launch
+void tn_plan256_splits(TnPlan& pl, int tiles, int Kc) {
   const int nk = Kc / BKR;
   int s = 256 / tiles;
   const int max_s = mv_cdiv(nk, 16);    // at least 16 stages (512 contraction rows) per split
@@ -1770,10 +1826,18 @@ TnPlan tn_plan256(int M, int N, int Kc) {
   if (s < 1) s = 1;
   pl.steps_per_split = mv_cdiv(nk, s);
   pl.splits = mv_cdiv(nk, pl.steps_per_split);
+}
+TnPlan tn_plan256(int M, int N, int Kc) {
+  TnPlan pl;
+  pl.tiles_m = mv_cdiv(M, BM2);
+  pl.tiles_n = mv_cdiv(N, BN2);
+  tn_plan256_splits(pl, pl.tiles_m * pl.tiles_n, Kc);
   return pl;
 }
+// The TN force code: kernel family (0 auto | 128 | 256) + TN_FORCE_NO_GROUP when mv_gemm_tn_bf16_group must run its items one by one
+constexpr int TN_FORCE_NO_GROUP = 1000;
 bool tn_use_ring(int M, int N, int Kc) {
-  const int force = g_force_tn.load(std::memory_order_relaxed);                        // 128 | 256: tuning and tests
+  const int force = g_force_tn.load(std::memory_order_relaxed) % TN_FORCE_NO_GROUP;    // 128 | 256: tuning and tests
   if (Kc <= 0 || Kc % BKR != 0 || force == 128) return false;
   if (force == 256) return true;
   if (!((long)M * N >= 256L * 256 * 4 && Kc >= 4096)) return false;   // >= 4 tiles and a contraction long enough to split over the chip
@@ -2130,7 +2194,9 @@ extern "C" int mv_gemm_nt_i8(const void* A, int lda, const void* B, int ldb, voi
 
 extern "C" int mv_gemm_force_variant(int nt_variant, int tn_variant) {
   const bool nt_ok = nt_force_find(nt_variant) != nullptr;
-  const bool tn_ok = tn_variant == 0 || tn_variant == 128 || tn_variant == 256;
+  const int tn_family = tn_variant % TN_FORCE_NO_GROUP;
+  const bool tn_ok = (tn_variant == tn_family || tn_variant == tn_family + TN_FORCE_NO_GROUP) &&
+                     (tn_family == 0 || tn_family == 128 || tn_family == 256);
   MV_REQUIRE(nt_ok && tn_ok, MV_ERR_UNSUPPORTED);
   g_force_nt.store(nt_variant, std::memory_order_relaxed);
   g_force_tn.store(tn_variant, std::memory_order_relaxed);
@@ -2221,4 +2287,108 @@ extern "C" int mv_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, f
     return mv_colsum(A, MV_BF16, lda, colsum, accumulate, Kc, M, cs_ws, (size_t)colsum_parts(Kc) * (size_t)M * sizeof(float), stream);
   }
   return MV_OK;
+}
+
+// ---- grouped dW: several products over one contraction range in one equal-split launch -------------------------------
+// proj dW (9 tiles) and qkv dW (27 tiles) of a ViT-B attention block planned apart are 28 and 9 splits, two slab bursts and two
+// reduces; together they are 36 tiles x 7 splits -- the schedule of an fc dW launch.  The plan is tn_plan256's rule on the tile
+// TOTAL.  Slabs are [split][item blocks one after another, each [M][N] dense, starting on a multiple of 4 floats].
+namespace {
+inline size_t tn_group_block(const mv_tn_item& it) { return ((size_t)it.M * (size_t)it.N + 3) & ~(size_t)3; }
+inline int tn_group_tiles(const mv_tn_item& it) { return mv_cdiv(it.M, BM2) * mv_cdiv(it.N, BN2); }
+bool tn_group_shapes_ok(const mv_tn_item* items, int n_items, int Kc) {
+  if (!items || n_items < 1 || n_items > TN_GROUP_MAX || Kc < 0) return false;
+  for (int i = 0; i < n_items; ++i)
+    if (items[i].M <= 0 || items[i].N <= 0) return false;
+  return true;
+}
+// one launch for all items?  Every item must be a product the ring kernel would take on its own.
+bool tn_group_paired(const mv_tn_item* items, int n_items, int Kc) {
+  if (g_force_tn.load(std::memory_order_relaxed) >= TN_FORCE_NO_GROUP || Kc <= 0 || Kc % BKR != 0) return false;
+  for (int i = 0; i < n_items; ++i) {
+    const mv_tn_item& it = items[i];
+    if (!tn_use_ring(it.M, it.N, Kc) || (long)Kc * it.lda * 2 >= (1L << 32) || (long)Kc * it.ldb * 2 >= (1L << 32)) return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" size_t mv_gemm_tn_group_workspace_bytes(const mv_tn_item* items, int n_items, int Kc) {
+  if (!tn_group_shapes_ok(items, n_items, Kc)) return 0;
+  // the larger of the grouped plan and every item on its own: independent of the path taken later
+  size_t bytes = 0, block_sum = 0;
+  int tiles = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const size_t own = mv_gemm_tn_workspace_bytes(items[i].M, items[i].N, Kc);
+    if (own > bytes) bytes = own;
+    block_sum += tn_group_block(items[i]);
+    tiles += tn_group_tiles(items[i]);
+  }
+  const int kr = Kc & ~(BKR - 1);
+  if (kr > 0) {
+    TnPlan pl;
+    tn_plan256_splits(pl, tiles, kr);
+    const size_t grouped = (size_t)pl.splits * block_sum * sizeof(float) + 256;
+    if (grouped > bytes) bytes = grouped;
+  }
+  return bytes;
+}
+
+extern "C" int mv_gemm_tn_bf16_group(const mv_tn_item* items, int n_items, int Kc, float* workspace, size_t workspace_bytes,
+                                     mv_stream_t stream) {
+  MV_REQUIRE(tn_group_shapes_ok(items, n_items, Kc), MV_ERR_SHAPE);
+  MV_REQUIRE(mv_aligned16(workspace), MV_ERR_ALIGN);
+  MV_REQUIRE(workspace_bytes >= mv_gemm_tn_group_workspace_bytes(items, n_items, Kc), MV_ERR_WORKSPACE);
+  if (!tn_group_paired(items, n_items, Kc)) {       // the items one after another, each exactly as mv_gemm_tn_bf16 runs it
+    for (int i = 0; i < n_items; ++i) {
+      const mv_tn_item& it = items[i];
+      const int rc = mv_gemm_tn_bf16(it.A, it.lda, it.B, it.ldb, it.C, it.ldc, it.M, it.N, Kc, 0, nullptr, workspace, workspace_bytes,
+                                     stream);
+      if (rc != MV_OK) return rc;
+    }
+    return MV_OK;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TnGroup grp{};
+  TnReduceGroup red{};
+  int tiles = 0;
+  size_t off = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const mv_tn_item& it = items[i];
+    MV_REQUIRE(it.lda % 8 == 0 && it.ldb % 8 == 0 && it.lda >= ((it.M + 7) & ~7) && it.ldb >= ((it.N + 7) & ~7), MV_ERR_ALIGN);
+    MV_REQUIRE(mv_aligned16(it.A) && mv_aligned16(it.B) && mv_aligned16(it.C), MV_ERR_ALIGN);
+    MV_REQUIRE(it.ldc >= it.N, MV_ERR_SHAPE);
+    grp.A[i] = (const bf16_t*)it.A, grp.B[i] = (const bf16_t*)it.B;
+    grp.lda[i] = it.lda, grp.ldb[i] = it.ldb, grp.M[i] = it.M, grp.N[i] = it.N;
+    grp.tiles_n[i] = mv_cdiv(it.N, BN2);
+    grp.tile0[i] = tiles;
+    red.C[i] = it.C, red.off[i] = (long)off, red.ldc[i] = it.ldc, red.M[i] = it.M, red.N[i] = it.N;
+    tiles += tn_group_tiles(it);
+    off += tn_group_block(it);
+  }
+  TnPlan pl;
+  tn_plan256_splits(pl, tiles, Kc);
+  const bool direct = pl.splits == 1;
+  const long slab_stride = direct ? 0 : (long)off;
+  int blocks = 0;
+  for (int i = 0; i < TN_GROUP_MAX; ++i) {
+    if (i < n_items) {
+      grp.out[i] = direct ? items[i].C : workspace + red.off[i];
+      grp.ld_out[i] = direct ? items[i].ldc : items[i].N;
+      red.block0[i] = blocks;
+      int nb = mv_cdiv((long)items[i].M * items[i].N, 1024);      // one 16-byte access per thread in the dense form
+      blocks += nb > 1024 ? 1024 : nb;
+    } else {
+      grp.A[i] = grp.A[0], grp.B[i] = grp.B[0], grp.out[i] = grp.out[0];
+      grp.tiles_n[i] = 1;
+      grp.tile0[i] = 0x7fffffff;
+      red.block0[i] = 0x7fffffff;
+    }
+  }
+  for (int i = n_items; i <= TN_GROUP_MAX; ++i) red.block0[i] = blocks;
+  const int rc = mv_launch<gemm_tn_ring_kernel<4, false, true>>(MV_HERE, tiles * pl.splits, 512, 4 * RSTAGE_BYTES, s, grp.A[0], grp.lda[0],
+                                                                grp.B[0], grp.ldb[0], grp.out[0], (long)grp.ld_out[0], slab_stride,
+                                                                grp.M[0], grp.N[0], Kc, grp.tiles_n[0], tiles, pl.steps_per_split, grp);
+  if (rc != MV_OK || direct) return rc;
+  return mv_launch<splitk_reduce_group_kernel>(MV_HERE, blocks, 256, 0, s, workspace, slab_stride, pl.splits, red);
 }

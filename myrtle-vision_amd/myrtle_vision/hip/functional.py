@@ -630,8 +630,11 @@ class _AttnBlock(Function):
         d_act, dbo = _take_side(dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
         if d_act is None:
             d_act = ops.cast(dout, adt).view(M, D)                # dY of the projection, activation dtype
-        dwo, dbo2 = ops.linear_dw(d_act, o.view(M, inner), M, D, inner, want_bias=dbo is None, weight=wo, bias=bo)
-        dbo = dbo if dbo is not None else dbo2
+        # bf16: dW of to_out is computed below, with dW of to_qkv, in one grouped split-K launch (d_act and o stay alive)
+        pair = adt == torch.bfloat16
+        if not pair:
+            dwo, dbo2 = ops.linear_dw(d_act, o.view(M, inner), M, D, inner, want_bias=dbo is None, weight=wo, bias=bo)
+            dbo = dbo if dbo is not None else dbo2
         do = torch.empty(B, T, inner, dtype=adt, device=x.device)
         ops.linear_dx(d_act, M, D, wo, do, inner)
         dbqkv = None
@@ -645,7 +648,12 @@ class _AttnBlock(Function):
                                                    B, T, heads, dh, scale), adt)
         else:
             dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale)
-        dwqkv, dbq2 = ops.linear_dw(dqkv.view(M, inner3), y, M, inner3, D, want_bias=dbqkv is None, weight=wqkv, bias=bqkv)
+        if pair:
+            (dwo, dbo2), (dwqkv, dbq2) = ops.linear_dw_pair(M, (d_act, o.view(M, inner), D, inner, wo, bo, dbo is None),
+                                                            (dqkv.view(M, inner3), y, inner3, D, wqkv, bqkv, dbqkv is None))
+            dbo = dbo if dbo is not None else dbo2
+        else:
+            dwqkv, dbq2 = ops.linear_dw(dqkv.view(M, inner3), y, M, inner3, D, want_bias=dbqkv is None, weight=wqkv, bias=bqkv)
         dbqkv = dbqkv if dbqkv is not None else dbq2
         dy = torch.empty(M, D, dtype=adt, device=x.device)
         ops.linear_dx(dqkv.view(M, inner3), M, inner3, wqkv, dy, D)

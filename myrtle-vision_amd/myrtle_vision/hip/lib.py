@@ -39,6 +39,8 @@ SIGNATURES = {
     "mv_layernorm_fwd_q8": ("plppp" "ii" "ff" "i" "p", _I),
     "mv_attention_fwd_f32_q8": ("pp" "iii" "f" "f" "i" "p", _I),
     "mv_gemm_tn_bf16": ("pipipi" "iii" "i" "p" "pz" "p", _I),
+    "mv_gemm_tn_group_workspace_bytes": ("pii", _Z),
+    "mv_gemm_tn_bf16_group": ("pii" "pz" "p", _I),
     "mv_gemm_f32": ("pllll" "pllll" "pllll" "iii" "ii" "fi" "pi" "pli" "pl" "p", _I),
     "mv_attention_bwd_force": ("i", _I),
     "mv_attention_fwd_force": ("i", _I),

@@ -763,14 +763,18 @@ def linear_dx(dy, M, N, weight, out, ldc, *, ld_dy=None, epi=EPI_NONE, aux=None,
     return out
 
 
-def linear_dw(dy, x, M, N, K, *, ld_dy=None, ldx=None, want_bias=True, weight=None, bias=None):
+def linear_dw(dy, x, M, N, K, *, ld_dy=None, ldx=None, want_bias=True, weight=None, bias=None, _pair=None):
     """dW[N, K] = dy[M, N]^T @ x[M, K] (fp32), db[N] = column sums of dy.  ``weight`` / ``bias`` (the parameters, optional)
-    select the gradient destinations (``grad_out``)."""
+    select the gradient destinations (``grad_out``).  ``_pair`` belongs to ``linear_dw_pair`` alone."""
+    if _pair is not None and type(_pair) is not _DwPair:
+        raise TypeError("linear_dw: _pair is linear_dw_pair's own argument (the gradients it returns are not computed yet)")
     ld_dy = N if ld_dy is None else ld_dy
     ldx = K if ldx is None else ldx
     dw = grad_out(weight, (N, K), x.device)
     db = grad_out(bias, (N,), x.device) if want_bias else None
-    if dy.dtype == torch.bfloat16:
+    if _pair is not None and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16:
+        _pair.append((dy, x, M, N, K, ld_dy, ldx, dw, db))         # linear_dw_pair computes it, before it returns
+    elif dy.dtype == torch.bfloat16:
         nbytes = lib().mv_gemm_tn_workspace_bytes(N, K, M)
         ws = workspace(nbytes, x.device)
         t0 = _timer.begin() if _timer is not None else None
@@ -798,6 +802,49 @@ def linear_dw(dy, x, M, N, K, *, ld_dy=None, ldx=None, want_bias=True, weight=No
         if want_bias:
             colsum(dy, M, N, ld_dy, db)
     return dw, db
+
+
+class _TnItem(ctypes.Structure):                  # mv_tn_item (include/myrtle_vision_hip.h)
+    _fields_ = [("A", ctypes.c_void_p), ("lda", ctypes.c_int), ("B", ctypes.c_void_p), ("ldb", ctypes.c_int),
+                ("C", ctypes.c_void_p), ("ldc", ctypes.c_int), ("M", ctypes.c_int), ("N", ctypes.c_int)]
+
+
+class _DwPair(list):
+    """The products ``linear_dw`` left for ``linear_dw_pair`` to compute; only ``linear_dw_pair`` makes one."""
+
+
+def linear_dw_pair(M, first, second):
+    """Two weight gradients over the same ``M`` token rows; each of ``first`` / ``second`` is ``(dy [M, N], x [M, K], N, K, weight,
+    bias, want_bias)``.  Returns ``((dw, db), (dw, db))``, both complete, as two ``linear_dw`` calls would.  bf16 products go to
+    the library as ONE group (mv_gemm_tn_bf16_group: one split-K launch and one reduce where the shapes allow it, otherwise one
+    after the other as mv_gemm_tn_bf16 runs them); any other dtype is two plain ``linear_dw`` calls.  Both go through
+    ``linear_dw``, the hook the dispatch tests replace."""
+    waiting = _DwPair()
+    outs = [linear_dw(dy, x, M, N, K, want_bias=want_bias, weight=weight, bias=bias, _pair=waiting)
+            for dy, x, N, K, weight, bias, want_bias in (first, second)]
+    if waiting:
+        _linear_dw_group(waiting)
+    return outs
+
+
+def _linear_dw_group(products):
+    """The bf16 products ``(dy, x, M, N, K, ld_dy, ldx, dw, db)`` -- all over the same ``M`` rows -- in one grouped split-K launch
+    (mv_gemm_tn_bf16_group).  The library runs them one after another, as ``mv_gemm_tn_bf16`` would, where they cannot share one."""
+    M = products[0][2]
+    items = (_TnItem * len(products))()
+    for it, (dy, x, m, N, K, ld_dy, ldx, dw, _db) in zip(items, products):
+        assert m == M and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+        it.A, it.lda, it.B, it.ldb, it.C, it.ldc, it.M, it.N = _p(dy), ld_dy, _p(x), ldx, _p(dw), K, N, K
+    addr = ctypes.addressof(items)
+    ws = workspace(lib().mv_gemm_tn_group_workspace_bytes(addr, len(products), M), products[0][1].device)
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().mv_gemm_tn_bf16_group(addr, len(products), M, _p(ws), ws.numel(), _s()), "gemm_tn_bf16_group", Kc=M,
+          shapes=[(pr[3], pr[4]) for pr in products])
+    if t0 is not None:
+        _timer.end("gemm_tn_bf16_group(+reduce)", t0, 2.0 * M * sum(pr[3] * pr[4] for pr in products), shape=f"dw x{len(products)}")
+    for dy, _x, _m, N, _K, ld_dy, _ldx, _dw, db in products:
+        if db is not None:
+            colsum(dy, M, N, ld_dy, db)
 
 
 def f32_dw_splits(M, N, K):

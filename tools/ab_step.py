@@ -4,7 +4,8 @@ blocks of STEPS steps for ROUNDS rounds (cdna guide rule 24); prints mean, std a
 
     NT_VARIANTS=3000,3002 ROUNDS=10 STEPS=10 python tools/ab_step.py      # column bands off / on (compare PAIRS only: with more
                                                                            # than two arms each one always follows the same predecessor)
-    GELU_BITS=8,16 ROUNDS=8 python tools/ab_step.py        # instead: width of the gelu' the MLP block keeps (functional.GELU_GRAD_BITS)
+    TN_VARIANTS=1000,0 python tools/ab_step.py             # instead: dW force codes; 1000 = to_out / to_qkv dW one by one, 0 = grouped
+    GELU_BITS=8,16 ROUNDS=8 python tools/ab_step.py       # instead: width of the gelu' the MLP block keeps (functional.GELU_GRAD_BITS)
     LIBS=a.so,b.so python tools/ab_step.py                 # instead: two BUILDS of the library take turns in the one process (variants
                                                            # 0 and 1; both are loaded, every op goes through the selected handle)
 """
