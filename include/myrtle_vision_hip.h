@@ -632,6 +632,28 @@ int mv_adamw(float* p, const float* g, float* m, float* v, long n, float lr, flo
  * graph) then stays valid while the learning-rate schedule and the step count advance: the host rewrites three floats. */
 int mv_adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
                  float weight_decay, float grad_scale, const float* clip_coef, mv_stream_t stream);
+/* the same step over a WHOLE parameter arena in one launch, with a learning-rate scale and a weight decay per tensor and an
+ * optional weight EMA (an extension: layer-wise learning-rate decay, a no_weight_decay list and a model EMA, as timm's
+ * create_optimizer(layer_decay=...) / ModelEmaV2 give the fine-tuning recipes; the reference has none of them).
+ * Work list, cut on the host once and kept on the device: item i covers elements [item_off[i], item_off[i] + item_len[i]) of
+ * p / g / m / v (and ema), never crosses a tensor, has 1 <= item_len[i] <= 4096, starts on a multiple of 8 elements (32 bytes:
+ * a tensor's arena offset plus a multiple of 4096) and belongs to segment item_seg[i] in [0, n_seg).  A segment is a distinct
+ * pair (lr_scale, weight_decay): seg_lr_scale[n_seg], seg_wd[n_seg], device fp32.  Workgroups stride over the items; within an
+ * item float4 accesses over item_len & ~3 elements and scalar ones for the rest.  Per element the arithmetic of mv_adamw with
+ * lr * seg_lr_scale[seg] for lr and seg_wd[seg] for weight_decay: with every scale 1 the same bits as mv_adamw writes over a
+ * region whose length is a multiple of 4 (every region of a parameter arena).
+ * (lr, bias_corr1, bias_corr2) come from the arguments, or from the device fp32 [3] hyper when that is non-null (mv_adamw_dev's
+ * form, what a captured launch needs); grad_scale and the device scalar clip_coef (may be null) as in mv_adamw.
+ * ema non-null: also ema[i] = ema_decay * ema[i] + (1 - ema_decay) * p_new[i], in the same pass.
+ * Elements in no item (the alignment gaps between tensors) are neither read nor written.  No atomics, every element has one
+ * owner: bitwise reproducible.  The items are trusted (a segment index or an extent outside the arrays is not detected).
+ * Checks, in this order and before any launch: n_items < 0 or n_seg <= 0 -> MV_ERR_SHAPE; a beta outside [0, 1), or ema non-null
+ * with ema_decay outside [0, 1) or NaN -> MV_ERR_UNSUPPORTED; n_items == 0 -> MV_OK, nothing launched; p / g / m / v null, any
+ * of them or ema not 16-byte aligned, or a null item or segment table -> MV_ERR_ALIGN. */
+int mv_adamw_table(float* p, const float* g, float* m, float* v, float* ema, const int64_t* item_off, const int32_t* item_len,
+                   const int32_t* item_seg, long n_items, const float* seg_lr_scale, const float* seg_wd, int n_seg,
+                   const float* hyper, float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
+                   float grad_scale, const float* clip_coef, float ema_decay, mv_stream_t stream);
 /* ---- gradient clipping: torch.nn.utils.clip_grad_norm_(vit.parameters(), clip_grad), classification/train.py:265-270 ----
  * over the flat gradient array g[n]: out[0] = total_norm = ||g * grad_scale||_2, out[1] = min(1, max_norm / (total_norm + 1e-6)).
  * out stays on the device; pass out + 1 as mv_adamw's clip_coef (it multiplies every gradient there: no extra pass).

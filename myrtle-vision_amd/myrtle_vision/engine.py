@@ -282,6 +282,22 @@ def _seg_loss_spec(task, train_config, num_classes=None):
     return spec
 
 
+def _has_ema(optimizer):
+    """Whether the optimizer keeps a weight EMA (``train_config["model_ema_decay"]``, utils/optim.py TableAdamW)."""
+    return getattr(optimizer, "ema", None) is not None
+
+
+def _start_ema(optimizer):
+    """After checkpoint load and the parameter broadcast: the EMA starts from the weights, unless the checkpoint carried one."""
+    if _has_ema(optimizer) and not optimizer.ema_loaded:
+        optimizer.reset_ema()
+
+
+def _ema_state(optimizer, vit):
+    """``save_checkpoint``'s ``model_ema``: the EMA as a full model state dict, or None without an EMA."""
+    return optimizer.ema_state_dict(vit) if _has_ema(optimizer) else None
+
+
 @torch.no_grad()
 def validation(val_loader, device, criterion, vit, task, num_classes):
     total_loss, total_acc, n = 0.0, 0.0, max(len(val_loader), 1)
@@ -361,6 +377,7 @@ def train_worker(rank, num_gpus, config, task="classification"):
     optimizer.arena.bump_versions()
     reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())   # MV_DDP_EXCHANGE=bf16: half-width, opt-in
     broadcast_parameters(optimizer.arena)
+    _start_ema(optimizer)
     optimizer.grad_scale = reducer.grad_scale
     # classification/train.py:265-270 (clip_grad_norm_ after EVERY backward, on the running accumulated gradient): the norm is
     # taken over the flat (all-reduced) gradient arena; on the last micro-batch of a window the coefficient is applied inside the
@@ -374,7 +391,7 @@ def train_worker(rank, num_gpus, config, task="classification"):
     epoch_offset = max(0, int(batch_size * world * iteration / max(len(trainset), 1)))
     if num_gpus > 1:
         dist.barrier()
-    n_accum, last_val = 0, (0.0, 0.0, None)
+    n_accum, last_val, last_val_ema = 0, (0.0, 0.0, None), None
     num_classes = data_config["number_of_classes"]
     for epoch in range(epoch_offset, train_config["epochs"]):
         epoch_loss = epoch_acc = 0.0
@@ -384,13 +401,20 @@ def train_worker(rank, num_gpus, config, task="classification"):
         for imgs, labels in train_loader:
             if iteration % train_config["iters_per_checkpoint"] == 0 and n_accum == 0 and rank == 0:
                 save_checkpoint(model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler, iteration=iteration,
-                                filepath=f"{out_dir}/vit_{iteration:06}")
+                                filepath=f"{out_dir}/vit_{iteration:06}", model_ema=_ema_state(optimizer, vit))
             if iteration % train_config["iters_per_val"] == 0 and n_accum == 0 and rank == 0:
                 last_val = validation(val_loader, device, criterion, vit, task, num_classes)
                 if scalars is not None:                          # segmentation/train.py:69-71
                     scalars.add_scalar("accuracy", last_val[1], iteration)
                     scalars.add_scalar("loss", last_val[0], iteration)
                     scalars.add_scalar("miou", last_val[2], iteration)
+                if _has_ema(optimizer):                          # the same validation on the weight EMA, logged beside it
+                    with optimizer.ema_weights():
+                        last_val_ema = validation(val_loader, device, criterion, vit, task, num_classes)
+                    if scalars is not None:
+                        scalars.add_scalar("accuracy_ema", last_val_ema[1], iteration)
+                        scalars.add_scalar("loss_ema", last_val_ema[0], iteration)
+                        scalars.add_scalar("miou_ema", last_val_ema[2], iteration)
             if n_accum == 0:
                 optimizer.zero_grad()
             reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
@@ -429,6 +453,10 @@ def train_worker(rank, num_gpus, config, task="classification"):
             extra = f" - val_miou: {last_val[2]:.4f}" if last_val[2] is not None else ""
             if train_miou is not None:                           # this rank's batches of the epoch
                 extra = f" - train_miou: {train_miou.get_miou():.4f}" + extra
+            if last_val_ema is not None:
+                extra += f" - val_loss_ema : {last_val_ema[0]:.4f} - val_acc_ema: {last_val_ema[1]:.4f}"
+                if last_val_ema[2] is not None:
+                    extra += f" - val_miou_ema: {last_val_ema[2]:.4f}"
             print(f"Epoch : {epoch + 1} - loss : {epoch_loss:.4f} - acc: {epoch_acc:.4f} - "
                   f"val_loss : {last_val[0]:.4f} - val_acc: {last_val[1]:.4f}{extra}\n")
     if scalars is not None:
@@ -474,7 +502,9 @@ def evaluate(config, task, quantize=False, calib_steps=0, quantized_ckpt=False):
         vit_config["q_format"] = "FP32"                                    # test_quantize.py:90-94: build FP32, load, then prepare
     vit, _ = get_models(config)
     vit = vit.to("cuda")
-    load_checkpoint(model=vit, optimizer=None, lr_scheduler=None, filepath=train_config["checkpoint_path"])
+    # "use_ema": true (top level or in train_config): evaluate the weight EMA the checkpoint carries under "model_ema"
+    use_ema = bool(config.get("use_ema", train_config.get("use_ema", False)))
+    load_checkpoint(model=vit, optimizer=None, lr_scheduler=None, filepath=train_config["checkpoint_path"], use_ema=use_ema)
     mk, collate = _datasets(task, data_config)
     dev = torch.device("cuda")
     if task == "detection":
@@ -662,6 +692,7 @@ def _train_detection(rank, num_gpus, config):
     optimizer.arena.bump_versions()
     reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())
     broadcast_parameters(optimizer.arena)
+    _start_ema(optimizer)
     optimizer.grad_scale = reducer.grad_scale
     optimizer.max_grad_norm = optimizer_args.clip_grad         # the clip sequence of train_worker, see there
     clip_every = optimizer_args.clip_grad is not None and n_batch_accum > 1
@@ -701,13 +732,19 @@ def _train_detection(rank, num_gpus, config):
             print(f"Epoch {epoch} validation...")
         val_loss, ap, _ = detection_validation(coco_from_dataset(valset), val_loader, criterion, weight_dict, vit,
                                                verbose=(rank == 0))
+        ema_row = {}
+        if _has_ema(optimizer):                                # every rank, like the plain validation: the evaluator gathers
+            with optimizer.ema_weights():
+                val_loss_ema, ap_ema, _ = detection_validation(coco_from_dataset(valset), val_loader, criterion, weight_dict, vit,
+                                                               verbose=(rank == 0))
+            ema_row = {"val_loss_ema": val_loss_ema, "ap_ema": ap_ema}
         if ap >= top_ap and rank == 0:
             save_checkpoint(model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler, iteration=iteration,
-                            filepath=f"{out_dir}/vit_epoch{epoch}")
+                            filepath=f"{out_dir}/vit_epoch{epoch}", model_ema=_ema_state(optimizer, vit))
         top_ap = max(top_ap, ap)
         lr_scheduler.step(epoch)
         if rank == 0:
-            log.write(epoch=epoch, loss=epoch_loss, val_loss=val_loss, ap=ap, lr=optimizer.param_groups[0]["lr"])
+            log.write(epoch=epoch, loss=epoch_loss, val_loss=val_loss, ap=ap, lr=optimizer.param_groups[0]["lr"], **ema_row)
             print(f"Epoch : {epoch + 1} - loss : {epoch_loss:.4f} - val_loss : {val_loss:.4f} - val_acc: {ap:.4f}\n")
     if num_gpus > 1:
         cleanup_distributed()

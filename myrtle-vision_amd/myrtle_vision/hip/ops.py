@@ -1880,6 +1880,27 @@ def adamw_step(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, step, grad_sc
                          grad_scale, _p(clip_coef), _s()), "adamw", n=p.numel())
 
 
+def adamw_table_step(p, g, m, v, items, seg_lr_scale, seg_wd, *, lr, beta1, beta2, eps, step, grad_scale=1.0, clip_coef=None,
+                     hyper=None, ema=None, ema_decay=0.0):
+    """In-place AdamW over a whole flat fp32 arena in ONE launch (``mv_adamw_table``).  ``items`` = (offsets int64 [n], lengths
+    int32 [n], segments int32 [n]) on the device, cut by ``utils.optim.build_items``; ``seg_lr_scale`` / ``seg_wd`` fp32 [n_seg]:
+    element i of an item of segment s steps at ``lr * seg_lr_scale[s]`` with weight decay ``seg_wd[s]``.  ``clip_coef`` and ``hyper``
+    as in ``adamw_step``.  ``ema`` (fp32, shaped like ``p``): ``ema = ema_decay * ema + (1 - ema_decay) * p_new`` in the same pass."""
+    off, length, seg = items
+    require_cuda(p, g, m, v, off, length, seg, seg_lr_scale, seg_wd, clip_coef, hyper, ema)
+    if not (off.dtype == torch.int64 and length.dtype == torch.int32 and seg.dtype == torch.int32
+            and off.numel() == length.numel() == seg.numel()):
+        raise ValueError("adamw_table_step: items are (int64 offsets, int32 lengths, int32 segments) of one length")
+    if not (g.numel() == m.numel() == v.numel() == p.numel() and (ema is None or ema.numel() == p.numel())):
+        raise ValueError("adamw_table_step: p, g, m, v (and ema) must have one size")
+    if seg_lr_scale.dtype != torch.float32 or seg_wd.dtype != torch.float32 or seg_lr_scale.numel() != seg_wd.numel():
+        raise ValueError("adamw_table_step: seg_lr_scale and seg_wd are fp32 tables of one length")
+    bc1, bc2 = (1.0, 1.0) if hyper is not None else (1.0 - beta1 ** step, 1.0 - beta2 ** step)
+    check(lib().mv_adamw_table(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(off), _p(length), _p(seg), off.numel(), _p(seg_lr_scale),
+                               _p(seg_wd), seg_wd.numel(), _p(hyper), 0.0 if hyper is not None else lr, beta1, beta2, eps, bc1, bc2,
+                               grad_scale, _p(clip_coef), float(ema_decay), _s()), "adamw_table", n=p.numel(), items=off.numel())
+
+
 def grad_norm_clip(g, max_norm, grad_scale=1.0):
     """-> fp32 [2] on the device: (total_norm of g * grad_scale, min(1, max_norm / (total_norm + 1e-6))) -- the two numbers
     of torch.nn.utils.clip_grad_norm_ (classification/train.py:265-270); no host synchronisation."""

@@ -77,24 +77,41 @@ def get_optimizer_args(train_config):
     a.cooldown_epochs = train_config["cooldown_epochs"]
     a.patience_epochs = train_config["patience_epochs"]
     a.decay_rate = train_config["decay_rate"]
+    # optional keys of the fine-tuning recipe (an extension, utils/optim.py TableAdamW): absent -> None -> the reference optimizer
+    a.layer_decay = train_config.get("layer_decay")
+    a.no_weight_decay = train_config.get("no_weight_decay")
+    a.model_ema_decay = train_config.get("model_ema_decay")
     return a
 
 
-def save_checkpoint(model, optimizer, lr_scheduler, iteration, filepath):
+def save_checkpoint(model, optimizer, lr_scheduler, iteration, filepath, model_ema=None):
+    """``model_ema`` (an extension): the weight EMA as a full model state dict (``TableAdamW.ema_state_dict``), written under
+    ``"model_ema"``; None keeps the reference's four keys."""
     ckpt = {
         "model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
         "optimizer": optimizer.state_dict(),
         "lr_scheduler": lr_scheduler.state_dict(),
         "iteration": iteration,
     }
+    if model_ema is not None:
+        ckpt["model_ema"] = {k: v.detach().cpu().clone() for k, v in model_ema.items()}
     torch.save(ckpt, filepath)
 
 
-def load_checkpoint(model, optimizer, lr_scheduler, filepath):
+def load_checkpoint(model, optimizer, lr_scheduler, filepath, use_ema=False):
+    """``use_ema`` (evaluation): the model takes the checkpoint's ``"model_ema"`` instead of ``"model"``; a checkpoint without
+    that key is an error.  An optimizer that keeps an EMA takes ``"model_ema"`` back when the checkpoint has one."""
     checkpoint = torch.load(filepath, map_location="cpu", weights_only=False)
-    model.load_state_dict(checkpoint["model"])
+    if use_ema:
+        if "model_ema" not in checkpoint:
+            raise KeyError(f"use_ema: checkpoint {filepath!r} has no 'model_ema' entry (it was trained without model_ema_decay)")
+        model.load_state_dict(checkpoint["model_ema"])
+    else:
+        model.load_state_dict(checkpoint["model"])
     if optimizer is not None:
         optimizer.load_state_dict(checkpoint["optimizer"])
+        if getattr(optimizer, "ema", None) is not None and "model_ema" in checkpoint:
+            optimizer.load_ema_state_dict(checkpoint["model_ema"])
     if lr_scheduler is not None:
         lr_scheduler.load_state_dict(checkpoint["lr_scheduler"])
     return checkpoint["iteration"]

@@ -16,6 +16,11 @@ MI355X-native layout: all trainable, *used* parameters live in ONE flat fp32 are
 (``ParamArena``); ``param.data`` and ``param.grad`` are views into it.  The optimizer step is then one kernel
 launch per group over 86 M contiguous elements (HBM-bound: 7 x 4 B per element), ``zero_grad`` is one memset, and
 the DDP gradient all-reduce (``utils/ddp.py``) works on contiguous slices of the same buffer with no packing.
+
+An extension beyond the reference: the optional ``train_config`` keys ``layer_decay``, ``no_weight_decay`` and ``model_ema_decay``
+(timm's layer-wise learning-rate decay and ``no_weight_decay`` list, a model EMA) select ``TableAdamW`` below -- a learning-rate
+scale and a weight decay per TENSOR and a weight EMA, stepped with ONE launch over the whole arena (``mv_adamw_table``).  Without
+the keys ``create_optimizer`` builds the ``AdamW`` described above and none of that code runs.
 """
 import math
 from typing import Iterable, List, Tuple
@@ -244,6 +249,228 @@ class AdamW:
             by_name[gname].update({k: v for k, v in s.items() if k in ("lr", "initial_lr", "weight_decay")})
 
 
+# ---- layer-wise learning-rate decay, weight-decay exemptions and a weight EMA: ONE launch over the arena (mv_adamw_table) ----------
+_LAYER0 = ("pos_embedding", "cls_token", "det_tokens", "pos_embedding_det")
+ITEM_MAX = 4096                          # elements per work item of mv_adamw_table (include/myrtle_vision_hip.h)
+
+
+def vit_depth(names) -> int:
+    """Number of transformer blocks among parameter names (``transformer.layers.{i}.*``)."""
+    blocks = [int(n.split(".")[2]) for n in names if n.startswith("transformer.layers.")]
+    return max(blocks) + 1 if blocks else 0
+
+
+def layer_ids(names, depth=None) -> List[int]:
+    """timm's ViT grouping for layer-wise learning-rate decay: 0 for the embeddings (``pos_embedding``, ``cls_token``,
+    ``patch_to_embedding.*``, ``det_tokens``, ``pos_embedding_det``), i + 1 for ``transformer.layers.{i}.*``, depth + 1 for
+    everything else (the decoder of any task)."""
+    names = list(names)
+    depth = vit_depth(names) if depth is None else depth
+    ids = []
+    for n in names:
+        if n in _LAYER0 or n.startswith("patch_to_embedding."):
+            ids.append(0)
+        elif n.startswith("transformer.layers."):
+            ids.append(int(n.split(".")[2]) + 1)
+        else:
+            ids.append(depth + 1)
+    return ids
+
+
+def layer_scales(names, layer_decay, depth=None) -> List[float]:
+    """``lr_scale = layer_decay ** (depth + 1 - layer_id)``: 1 for the head, ``layer_decay ** (depth + 1)`` for the embeddings."""
+    names = list(names)
+    depth = vit_depth(names) if depth is None else depth
+    return [float(layer_decay) ** (depth + 1 - i) for i in layer_ids(names, depth)]
+
+
+def build_items(offsets, sizes, pairs):
+    """Cut tensors into the work items of ``mv_adamw_table``.  ``offsets`` / ``sizes``: each tensor's arena offset (a multiple of 8)
+    and element count; ``pairs``: its ``(lr_scale, weight_decay)``.  -> (item offsets, item lengths, item segments, segments):
+    three lists of one length and the list of distinct pairs in order of first use.  An item never crosses a tensor, holds at most
+    ``ITEM_MAX`` elements and starts at its tensor's offset plus a multiple of ``ITEM_MAX``; the gaps between tensors are in no item."""
+    segments, index = [], {}
+    off, length, seg = [], [], []
+    for o, n, pair in zip(offsets, sizes, pairs):
+        pair = (float(pair[0]), float(pair[1]))
+        s = index.setdefault(pair, len(segments))
+        if s == len(segments):
+            segments.append(pair)
+        for k in range(0, n, ITEM_MAX):
+            off.append(o + k)
+            length.append(min(ITEM_MAX, n - k))
+            seg.append(s)
+    return off, length, seg, segments
+
+
+def _check_unit(key, value, hi_closed=True):
+    """A float in (0, 1] (``hi_closed``) or (0, 1); the message names ``key``."""
+    ok = isinstance(value, (int, float)) and not isinstance(value, bool) and value == value
+    ok = ok and 0.0 < value and (value <= 1.0 if hi_closed else value < 1.0)
+    if not ok:
+        raise ValueError(f"{key} must be a number in (0, 1{']' if hi_closed else ')'}, got {value!r}")
+    return float(value)
+
+
+class TableAdamW(AdamW):
+    """``AdamW`` with a learning-rate scale and a weight decay PER TENSOR and an optional weight EMA, stepped with ONE
+    ``mv_adamw_table`` launch over the whole arena (an extension; the reference has none of the three).
+
+    * ``layer_decay``: timm's layer-wise learning-rate decay (``layer_scales``); the effective rate of a tensor is the scheduled
+      base rate times its scale, through warm-up and down to ``min_lr``, as timm applies ``lr_scale``.
+    * ``no_weight_decay``: exact parameter names whose weight decay becomes 0 (the arena's layout does not change).
+    * ``ema_decay``: ``ema = d * ema + (1 - d) * p`` after every step, in the same pass; ``ema_weights()`` evaluates on it.
+
+    ``param_groups`` stays the two reference groups carrying the scheduled BASE rate, so ``CosineLRScheduler`` works unchanged; the
+    two must carry one rate."""
+
+    def __init__(self, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, layer_decay=None,
+                 no_weight_decay=(), ema_decay=None):
+        super().__init__(arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.layer_decay = None if layer_decay is None else _check_unit("layer_decay", layer_decay)
+        self.ema_decay = None if ema_decay is None else _check_unit("ema_decay", ema_decay, hi_closed=False)
+        if isinstance(no_weight_decay, str):
+            raise ValueError(f"no_weight_decay must be a list of parameter names, got the string {no_weight_decay!r}")
+        self.no_weight_decay = tuple(no_weight_decay)
+        known = set(arena.names) | set(arena.torch_groups[0]) | set(arena.torch_groups[1])
+        for n in self.no_weight_decay:
+            if n not in known:
+                raise ValueError(f"no_weight_decay names {n!r}, which is not a parameter of the model")
+        self.lr_scales = layer_scales(arena.names, self.layer_decay) if self.layer_decay is not None else [1.0] * len(arena.names)
+        self._tables_wd = None
+        self._refresh_tables()
+        self.ema, self.ema_loaded, self._in_ema = None, False, False
+        if self.ema_decay is not None:
+            self.ema = torch.zeros_like(arena.flat_param)
+            self.reset_ema()
+
+    def tensor_weight_decays(self) -> List[float]:
+        """Each arena tensor's weight decay: its group's, or 0 for a ``no_weight_decay`` name."""
+        a, exempt = self.arena, set(self.no_weight_decay)
+        by_name = {g["name"]: g["weight_decay"] for g in self.param_groups}
+        return [0.0 if n in exempt else float(by_name["decay" if o < a.n_decay else "no_decay"])
+                for n, o in zip(a.names, a.offsets)]
+
+    def _refresh_tables(self):
+        """(Re)build the device work list and segment tables; they change only when a group's weight decay does (a loaded checkpoint)."""
+        wd = tuple(g["weight_decay"] for g in self.param_groups)
+        if wd == self._tables_wd:
+            return
+        a = self.arena
+        dev = a.flat_param.device
+        off, length, seg, segments = build_items(a.offsets, [p.numel() for p in a.params],
+                                                 list(zip(self.lr_scales, self.tensor_weight_decays())))
+        self.items = (torch.tensor(off, dtype=torch.int64, device=dev), torch.tensor(length, dtype=torch.int32, device=dev),
+                      torch.tensor(seg, dtype=torch.int32, device=dev))
+        self.segments = segments
+        self.seg_lr_scale = torch.tensor([s for s, _ in segments], dtype=torch.float32, device=dev)
+        self.seg_wd = torch.tensor([w for _, w in segments], dtype=torch.float32, device=dev)
+        self._tables_wd = wd
+
+    @torch.no_grad()
+    def step(self):
+        if self._in_ema:
+            raise RuntimeError("step() inside ema_weights(): the parameters hold the EMA, not the trained weights")
+        lr = self.param_groups[0]["lr"]
+        if any(g["lr"] != lr for g in self.param_groups):
+            raise ValueError(f"the two param_groups carry different learning rates ({[g['lr'] for g in self.param_groups]}): the one "
+                             "launch steps at ONE scheduled rate times each tensor's scale")
+        self._refresh_tables()
+        self.arena.sync_grads()
+        if self._hyper is None:
+            self.step_count += 1
+        elif not torch.cuda.is_current_stream_capturing():
+            self.advance()                # inside a capture the replayer advances (utils/graph.py)
+        b1, b2 = self.defaults["betas"]
+        a = self.arena
+        coef = None
+        if self.max_grad_norm is not None:
+            self.last_grad_norm = ops.grad_norm_clip(a.flat_grad, self.max_grad_norm, self.grad_scale)
+            coef = self.last_grad_norm[1:2]
+        ops.adamw_table_step(a.flat_param, a.flat_grad, self.exp_avg, self.exp_avg_sq, self.items, self.seg_lr_scale, self.seg_wd,
+                             lr=lr, beta1=b1, beta2=b2, eps=self.defaults["eps"], step=self.step_count, grad_scale=self.grad_scale,
+                             clip_coef=coef, hyper=None if self._hyper is None else self._hyper[self.param_groups[0]["name"]],
+                             ema=self.ema, ema_decay=self.ema_decay if self.ema is not None else 0.0)
+        a.bump_versions()
+
+    # -- the weight EMA -------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def reset_ema(self):
+        """EMA <- the current weights (a fresh run, or after loading weights that carried no EMA)."""
+        if self.ema is None:
+            raise RuntimeError("reset_ema(): this optimizer was built without ema_decay")
+        self.ema.copy_(self.arena.flat_param)
+
+    def _swap_ema(self):
+        with torch.no_grad():
+            tmp = self.arena.flat_param.clone()
+            self.arena.flat_param.copy_(self.ema)
+            self.ema.copy_(tmp)
+        self.arena.bump_versions()
+
+    def ema_weights(self):
+        """``with optimizer.ema_weights(): validate(model)``: the parameters hold the EMA inside the block and the trained weights
+        again after it (the two buffers exchange contents, bit for bit)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def swapped():
+            if self.ema is None:
+                raise RuntimeError("ema_weights(): this optimizer was built without ema_decay")
+            if self._in_ema:
+                raise RuntimeError("ema_weights() does not nest")
+            self._swap_ema()
+            self._in_ema = True
+            try:
+                yield self
+            finally:
+                self._in_ema = False
+                self._swap_ema()
+        return swapped()
+
+    def ema_state_dict(self, model):
+        """The model's state dict (host tensors) with every arena parameter replaced by its EMA: a checkpoint's ``"model_ema"``."""
+        if self.ema is None:
+            raise RuntimeError("ema_state_dict(): this optimizer was built without ema_decay")
+        a = self.arena
+        sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+        src = self.arena.flat_param if self._in_ema else self.ema        # inside ema_weights() the buffers are exchanged
+        for n, p, o in zip(a.names, a.params, a.offsets):
+            if n not in sd:
+                raise KeyError(f"parameter {n!r} is not a key of the model's state dict")
+            sd[n] = src[o:o + p.numel()].view(p.shape).detach().cpu().clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        if self.ema is None:
+            raise RuntimeError("load_ema_state_dict(): this optimizer was built without ema_decay")
+        a = self.arena
+        for n, p, o in zip(a.names, a.params, a.offsets):
+            if n not in sd:
+                raise KeyError(f"'model_ema' has no entry {n!r}")
+            if tuple(sd[n].shape) != tuple(p.shape):
+                raise ValueError(f"'model_ema' entry {n}: shape {tuple(sd[n].shape)} != {tuple(p.shape)}")
+            self.ema[o:o + p.numel()].copy_(sd[n].reshape(-1))
+        self.ema_loaded = True
+
+    # -- checkpoints: AdamW's format plus two keys torch ignores -----------------------------------------------------------
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["layer_decay"] = self.layer_decay
+        sd["no_weight_decay"] = list(self.no_weight_decay)
+        return sd
+
+    def load_state_dict(self, sd):
+        if sd.get("layer_decay") != self.layer_decay:
+            raise ValueError(f"optimizer checkpoint has layer_decay={sd.get('layer_decay')!r}, this optimizer {self.layer_decay!r}")
+        if sorted(sd.get("no_weight_decay", ())) != sorted(self.no_weight_decay):
+            raise ValueError(f"optimizer checkpoint has no_weight_decay={list(sd.get('no_weight_decay', ()))!r}, this optimizer "
+                             f"{list(self.no_weight_decay)!r}")
+        super().load_state_dict(sd)
+        self._refresh_tables()
+
+
 class CosineLRScheduler:
     """timm 0.5.4 ``CosineLRScheduler`` restated for cycle_limit=1, t_in_epochs=True, no noise, warmup_prefix False."""
 
@@ -286,10 +513,28 @@ def create_optimizer(args, model, skip=None):
         raise NotImplementedError(f"optimizer {args.opt!r}: only 'adamw' (every reference train_config) is implemented")
     if skip is None:
         skip = model.unused_parameter_names() if hasattr(model, "unused_parameter_names") else ()
+    # optional train_config keys (an extension): any of them selects the one-launch TableAdamW; without them the object, its
+    # two launches and everything else are the reference optimizer's.  Checked before the arena takes over the parameters.
+    layer_decay, ema_decay = getattr(args, "layer_decay", None), getattr(args, "model_ema_decay", None)
+    no_weight_decay = getattr(args, "no_weight_decay", None)
+    if layer_decay is not None:
+        _check_unit("layer_decay", layer_decay)
+    if ema_decay is not None:
+        _check_unit("model_ema_decay", ema_decay, hi_closed=False)
+    if no_weight_decay is not None:
+        if not isinstance(no_weight_decay, (list, tuple)) or not all(isinstance(n, str) for n in no_weight_decay):
+            raise ValueError(f"no_weight_decay must be a list of parameter names, got {no_weight_decay!r}")
+        have = {n for n, _ in model.named_parameters()}
+        for n in no_weight_decay:
+            if n not in have:
+                raise ValueError(f"no_weight_decay names {n!r}, which is not a parameter of the model")
     arena = ParamArena(model.named_parameters(), skip=skip)
     betas = tuple(args.opt_betas) if getattr(args, "opt_betas", None) else (0.9, 0.999)
     eps = args.opt_eps if getattr(args, "opt_eps", None) is not None else 1e-8
-    return AdamW(arena, lr=args.lr, betas=betas, eps=eps, weight_decay=args.weight_decay)
+    if layer_decay is None and ema_decay is None and no_weight_decay is None:
+        return AdamW(arena, lr=args.lr, betas=betas, eps=eps, weight_decay=args.weight_decay)
+    return TableAdamW(arena, lr=args.lr, betas=betas, eps=eps, weight_decay=args.weight_decay, layer_decay=layer_decay,
+                      no_weight_decay=no_weight_decay or (), ema_decay=ema_decay)
 
 
 def create_scheduler(args, optimizer):
