@@ -18,6 +18,9 @@ seeding, batch-size solver, one process per GPU, rank-0 checkpoints every ``iter
 * ``pretrained_backbone`` must be a local timm-format state dict (no network); a bare timm model NAME that is not a
   file means "random init" with a warning.
 
+Both loops share one skeleton: ``_begin`` (device, seed, batch sizes, process group, output directory), ``_model_and_optimizer``,
+``_resume`` (checkpoint, reducer, broadcast, EMA start, first epoch) and one ``AccumWindow`` (zero_grad / exchange / clip / step).
+
 ``task="detection"`` follows detection/train.py:40-332 instead (``_train_detection``): padded batches of differently sized
 images, ``SetCriterion`` weighted by ``train_config``'s ``weight_dict`` keys, validation on EVERY rank once per epoch
 (``PostProcess`` -> ``CocoEvaluator`` -> validation loss) and a checkpoint ``vit_epoch{N}`` whenever AP@[.5:.95] does not drop.
@@ -282,20 +285,120 @@ def _seg_loss_spec(task, train_config, num_classes=None):
     return spec
 
 
-def _has_ema(optimizer):
-    """Whether the optimizer keeps a weight EMA (``train_config["model_ema_decay"]``, utils/optim.py TableAdamW)."""
-    return getattr(optimizer, "ema", None) is not None
-
-
-def _start_ema(optimizer):
-    """After checkpoint load and the parameter broadcast: the EMA starts from the weights, unless the checkpoint carried one."""
-    if _has_ema(optimizer) and not optimizer.ema_loaded:
-        optimizer.reset_ema()
-
-
 def _ema_state(optimizer, vit):
-    """``save_checkpoint``'s ``model_ema``: the EMA as a full model state dict, or None without an EMA."""
-    return optimizer.ema_state_dict(vit) if _has_ema(optimizer) else None
+    """``save_checkpoint``'s ``model_ema``: the weight EMA (``train_config["model_ema_decay"]``, utils/optim.py TableAdamW) as a full
+    model state dict, or None without an EMA."""
+    return optimizer.ema_state_dict(vit) if optimizer.ema is not None else None
+
+
+def _validate_twice(optimizer, validate):
+    """-> (``validate("")`` on the weights, ``validate("_ema")`` on the weight EMA or None without one), in that order; the argument
+    is the suffix of the metric names."""
+    plain = validate("")
+    if optimizer.ema is None:
+        return plain, None
+    with optimizer.ema_weights():
+        return plain, validate("_ema")
+
+
+def _begin(rank, num_gpus, train_config, dist_config):
+    """What either loop does first after its recipe-key checks: device, seed, batch sizes (written back into the caller's
+    ``train_config``), process group, output directory -> (device, world, batch_size, n_batch_accum, out_dir)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("training needs an MI355X: the myrtle_vision HIP path has no CPU fallback")
+    device = torch.device("cuda", rank)
+    torch.cuda.set_device(device)
+    seed_everything(train_config["seed"])
+    world = max(num_gpus, 1)
+    batch_size, n_batch_accum = get_batch_sizes(train_config["local_batch_size"], num_gpus,
+                                                train_config["global_batch_size"], verbose=(rank == 0))
+    train_config["local_batch_size"] = batch_size
+    train_config["global_batch_size"] = batch_size * n_batch_accum * world
+    train_config["n_batch_accum"] = n_batch_accum
+    if num_gpus > 1:
+        init_distributed(rank, num_gpus, **dist_config)
+    out_dir = train_config["output_directory"]
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        print("output directory:", out_dir)
+    return device, world, batch_size, n_batch_accum, out_dir
+
+
+def _model_and_optimizer(rank, config, data_config, device):
+    """After the loaders: the model (from a local ``pretrained_backbone`` if one is named) on the device, its optimizer and schedule
+    -> (vit, optimizer, lr_scheduler, optimizer_args)."""
+    train_config = config["train_config"]
+    vit, _ = get_models(config)
+    backbone = train_config.get("pretrained_backbone")
+    if backbone is not None:
+        if isinstance(backbone, str) and os.path.exists(backbone):
+            missing = vit.load_state_dict(rename_timm_state_dict(backbone, config["vit_config"], data_config["number_of_classes"]),
+                                          strict=False)
+            assert missing.unexpected_keys == []
+        elif rank == 0:
+            print(f"WARNING: pretrained_backbone={backbone!r} is not a local file (no network): training from random init")
+    vit = vit.to(device)
+    optimizer_args = get_optimizer_args(train_config)
+    optimizer = create_optimizer(optimizer_args, vit)          # leaves out vit.unused_parameter_names() (det tokens unless live)
+    lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
+    return vit, optimizer, lr_scheduler, optimizer_args
+
+
+class AccumWindow:
+    """One gradient-accumulation window of ``n_batch_accum`` micro-batches, the same in every loop: ``zero_grad`` at its start; the
+    exchange switched on for the LAST backward only -- or for every one when clipping between micro-batches (``clip_every``);
+    ``finish`` + ``clip_accumulated`` after each backward but the last; ``finish`` + ``step`` after the last.
+
+    ``clip_every`` is classification/train.py:265-270 (clip_grad_norm_ after EVERY backward, on the running accumulated gradient): the
+    norm is taken over the flat (all-reduced) gradient arena; on the last micro-batch of a window the coefficient is applied inside
+    the AdamW kernel, on the earlier ones the arena is rescaled in place (which needs the averaged gradient: those micro-batches are
+    exchanged too, as the reference's DDP does on every backward).
+
+    The window outlives the epoch: one opened by the last batches of an epoch is completed by the first batches of the next."""
+
+    def __init__(self, optimizer, reducer, n_batch_accum, clip_every):
+        self.optimizer, self.reducer, self.n_batch_accum, self.clip_every = optimizer, reducer, n_batch_accum, clip_every
+        self.n_accum = 0
+
+    @property
+    def at_start(self):
+        """No micro-batch of the current window has run: the only place for a checkpoint or a validation."""
+        return self.n_accum == 0
+
+    def backward(self, loss):
+        """``loss.backward()`` inside the window's sequence -> whether this micro-batch ended in an optimizer step."""
+        if self.n_accum == 0:
+            self.optimizer.zero_grad()
+        self.reducer.enabled = self.reducer.world > 1 and (self.clip_every or self.n_accum == self.n_batch_accum - 1)
+        loss.backward()
+        self.n_accum += 1
+        if self.n_accum < self.n_batch_accum:
+            if self.clip_every:
+                self.reducer.finish()
+                self.optimizer.clip_accumulated()
+            return False
+        self.n_accum = 0
+        self.reducer.finish()
+        self.optimizer.step()
+        return True
+
+
+def _resume(train_config, vit, optimizer, lr_scheduler, clip_grad, n_batch_accum, samples_per_iteration, n_train, num_gpus):
+    """After the criterion: the checkpoint (if any), the reducer, rank 0's parameters to every rank, the EMA's start, the clipping
+    set-up; then every rank waits for the others -> (iteration, the epoch it falls in, the accumulation window)."""
+    iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler)
+    optimizer.arena.bump_versions()
+    reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())   # MV_DDP_EXCHANGE=bf16: half-width, opt-in
+    broadcast_parameters(optimizer.arena)
+    if optimizer.ema is not None and not optimizer.ema_loaded:
+        optimizer.reset_ema()                                  # the EMA starts from the weights, unless the checkpoint carried one
+    optimizer.grad_scale = reducer.grad_scale
+    optimizer.max_grad_norm = clip_grad
+    window = AccumWindow(optimizer, reducer, n_batch_accum, clip_every=clip_grad is not None and n_batch_accum > 1)
+    epoch_offset = max(0, int(samples_per_iteration * iteration / max(n_train, 1)))
+    if num_gpus > 1:
+        dist.barrier()
+    return iteration, epoch_offset, window
 
 
 @torch.no_grad()
@@ -323,27 +426,11 @@ def train_worker(rank, num_gpus, config, task="classification"):
     if task == "detection":
         _seg_loss_spec(task, config["train_config"])           # the segmentation recipe key on this task: an error before any work
         return _train_detection(rank, num_gpus, config)
-    train_config, dist_config, vit_config = config["train_config"], config["dist_config"], config["vit_config"]
+    train_config = config["train_config"]
     data_config = parse_config(config["data_config_path"])
     train_criterion, mixer = _train_criterion(task, train_config)      # first: a recipe key on the wrong task fails before any work
     seg_spec = _seg_loss_spec(task, train_config, data_config["number_of_classes"])
-    if not torch.cuda.is_available():
-        raise RuntimeError("training needs an MI355X: the myrtle_vision HIP path has no CPU fallback")
-    device = torch.device("cuda", rank)
-    torch.cuda.set_device(device)
-    seed_everything(train_config["seed"])
-    world = max(num_gpus, 1)
-    batch_size, n_batch_accum = get_batch_sizes(train_config["local_batch_size"], num_gpus,
-                                                train_config["global_batch_size"], verbose=(rank == 0))
-    train_config["local_batch_size"] = batch_size
-    train_config["global_batch_size"] = batch_size * n_batch_accum * world
-    train_config["n_batch_accum"] = n_batch_accum
-    if num_gpus > 1:
-        init_distributed(rank, num_gpus, **dist_config)
-    out_dir = train_config["output_directory"]
-    if rank == 0:
-        os.makedirs(out_dir, exist_ok=True)
-        print("output directory:", out_dir)
+    device, world, batch_size, n_batch_accum, out_dir = _begin(rank, num_gpus, train_config, config["dist_config"])
 
     mk, collate = _datasets(task, data_config)
     use_dev = train_config.get("device_transforms", True)
@@ -356,68 +443,34 @@ def train_worker(rank, num_gpus, config, task="classification"):
     val_loader = BatchFeed(valset, plan_v, task, device, collate, batch_size=batch_size,
                            drop_last=train_config["drop_last_batch"])
 
-    vit, _ = get_models(config)
-    backbone = train_config.get("pretrained_backbone")
-    if backbone is not None:
-        if isinstance(backbone, str) and os.path.exists(backbone):
-            missing = vit.load_state_dict(rename_timm_state_dict(backbone, vit_config, data_config["number_of_classes"]),
-                                          strict=False)
-            assert missing.unexpected_keys == []
-        elif rank == 0:
-            print(f"WARNING: pretrained_backbone={backbone!r} is not a local file (no network): training from random init")
-    vit = vit.to(device)
-
-    optimizer_args = get_optimizer_args(train_config)
-    optimizer = create_optimizer(optimizer_args, vit)
-    lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
+    vit, optimizer, lr_scheduler, optimizer_args = _model_and_optimizer(rank, config, data_config, device)
     # validation keeps the plain criterion; without a recipe key it IS the training criterion, the reference's CrossEntropyLoss()
     criterion = train_criterion if type(train_criterion) is CrossEntropyLoss else CrossEntropyLoss()
-    iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer,
-                                            lr_scheduler=lr_scheduler)
-    optimizer.arena.bump_versions()
-    reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())   # MV_DDP_EXCHANGE=bf16: half-width, opt-in
-    broadcast_parameters(optimizer.arena)
-    _start_ema(optimizer)
-    optimizer.grad_scale = reducer.grad_scale
-    # classification/train.py:265-270 (clip_grad_norm_ after EVERY backward, on the running accumulated gradient): the norm is
-    # taken over the flat (all-reduced) gradient arena; on the last micro-batch of a window the coefficient is applied inside the
-    # AdamW kernel, on the earlier ones the arena is rescaled in place (which needs the averaged gradient: those micro-batches are
-    # exchanged too, as the reference's DDP does on every backward)
-    optimizer.max_grad_norm = optimizer_args.clip_grad
-    clip_every = optimizer_args.clip_grad is not None and n_batch_accum > 1
+    iteration, epoch_offset, window = _resume(train_config, vit, optimizer, lr_scheduler, optimizer_args.clip_grad, n_batch_accum,
+                                              batch_size * world, len(trainset), num_gpus)
     scalars = _Scalars(train_config.get("tensorboard_dir", "runs/")) if (task == "segmentation" and rank == 0) else None
+    num_classes = data_config["number_of_classes"]
+
+    def validate(suffix):
+        val = validation(val_loader, device, criterion, vit, task, num_classes)
+        if scalars is not None:                                  # segmentation/train.py:69-71
+            for tag, value in (("accuracy", val[1]), ("loss", val[0]), ("miou", val[2])):
+                scalars.add_scalar(tag + suffix, value, iteration)
+        return val
 
     vit.train()
-    epoch_offset = max(0, int(batch_size * world * iteration / max(len(trainset), 1)))
-    if num_gpus > 1:
-        dist.barrier()
-    n_accum, last_val, last_val_ema = 0, (0.0, 0.0, None), None
-    num_classes = data_config["number_of_classes"]
+    last_val, last_val_ema = (0.0, 0.0, None), None
     for epoch in range(epoch_offset, train_config["epochs"]):
         epoch_loss = epoch_acc = 0.0
         train_miou = MIoU(num_classes, device) if seg_spec is not None else None
         if sampler is not None:
             sampler.set_epoch(epoch)
         for imgs, labels in train_loader:
-            if iteration % train_config["iters_per_checkpoint"] == 0 and n_accum == 0 and rank == 0:
+            if iteration % train_config["iters_per_checkpoint"] == 0 and window.at_start and rank == 0:
                 save_checkpoint(model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler, iteration=iteration,
                                 filepath=f"{out_dir}/vit_{iteration:06}", model_ema=_ema_state(optimizer, vit))
-            if iteration % train_config["iters_per_val"] == 0 and n_accum == 0 and rank == 0:
-                last_val = validation(val_loader, device, criterion, vit, task, num_classes)
-                if scalars is not None:                          # segmentation/train.py:69-71
-                    scalars.add_scalar("accuracy", last_val[1], iteration)
-                    scalars.add_scalar("loss", last_val[0], iteration)
-                    scalars.add_scalar("miou", last_val[2], iteration)
-                if _has_ema(optimizer):                          # the same validation on the weight EMA, logged beside it
-                    with optimizer.ema_weights():
-                        last_val_ema = validation(val_loader, device, criterion, vit, task, num_classes)
-                    if scalars is not None:
-                        scalars.add_scalar("accuracy_ema", last_val_ema[1], iteration)
-                        scalars.add_scalar("loss_ema", last_val_ema[0], iteration)
-                        scalars.add_scalar("miou_ema", last_val_ema[2], iteration)
-            if n_accum == 0:
-                optimizer.zero_grad()
-            reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
+            if iteration % train_config["iters_per_val"] == 0 and window.at_start and rank == 0:
+                last_val, last_val_ema = _validate_twice(optimizer, validate)    # the EMA's figures are logged beside the plain ones
             if seg_spec is not None:                             # class weights / smoothing / Dice: the fused tail or an error
                 loss, acc_t, _, areas = vit.segmentation_loss(imgs, labels, loss=seg_spec, return_areas=True)
                 train_miou.add_areas(areas)                      # counted by the loss kernel: no second pass, no synchronisation
@@ -433,15 +486,7 @@ def train_worker(rank, num_gpus, config, task="classification"):
                     imgs, lam = mixer(imgs, labels)              # in place; the labels stay the original ones
                 loss, pred = train_criterion(vit(imgs), labels, lam)
                 acc_t = (pred == labels).float().mean()          # the kernel's arg-max against the ORIGINAL labels
-            loss.backward()
-            n_accum += 1
-            if clip_every and n_accum < n_batch_accum:
-                reducer.finish()
-                optimizer.clip_accumulated()
-            if n_accum == n_batch_accum:
-                n_accum = 0
-                reducer.finish()
-                optimizer.step()
+            if window.backward(loss):
                 iteration += 1
                 if rank == 0:
                     acc = float(acc_t) if acc_t is not None else float((outputs.argmax(dim=1) == labels).float().mean())
@@ -631,25 +676,9 @@ def _train_detection(rank, num_gpus, config):
     from myrtle_vision.datasets.coco import coco_from_dataset
     from myrtle_vision.models.detector import SetCriterion
     from myrtle_vision.models.matcher import HungarianMatcher
-    train_config, dist_config, vit_config = config["train_config"], config["dist_config"], config["vit_config"]
+    train_config = config["train_config"]
     data_config = parse_config(config["data_config_path"])
-    if not torch.cuda.is_available():
-        raise RuntimeError("training needs an MI355X: the myrtle_vision HIP path has no CPU fallback")
-    device = torch.device("cuda", rank)
-    torch.cuda.set_device(device)
-    seed_everything(train_config["seed"])
-    world = max(num_gpus, 1)
-    batch_size, n_batch_accum = get_batch_sizes(train_config["local_batch_size"], num_gpus,
-                                                train_config["global_batch_size"], verbose=(rank == 0))
-    train_config["local_batch_size"] = batch_size
-    train_config["global_batch_size"] = batch_size * n_batch_accum * world
-    train_config["n_batch_accum"] = n_batch_accum
-    if num_gpus > 1:
-        init_distributed(rank, num_gpus, **dist_config)
-    out_dir = train_config["output_directory"]
-    if rank == 0:
-        os.makedirs(out_dir, exist_ok=True)
-        print("output directory:", out_dir)
+    device, world, batch_size, n_batch_accum, out_dir = _begin(rank, num_gpus, train_config, config["dist_config"])
 
     mk, collate = _datasets("detection", data_config)
     use_dev = train_config.get("device_transforms", True)
@@ -668,83 +697,48 @@ def _train_detection(rank, num_gpus, config):
     val_loader = BatchFeed(valset, plan_v, "detection", device, collate, sampler=val_sampler, batch_size=batch_size,
                            drop_last=train_config["drop_last_batch"])
 
-    vit, _ = get_models(config)
-    backbone = train_config.get("pretrained_backbone")
-    if backbone is not None:
-        if isinstance(backbone, str) and os.path.exists(backbone):
-            missing = vit.load_state_dict(rename_timm_state_dict(backbone, vit_config, data_config["number_of_classes"]),
-                                          strict=False)
-            assert missing.unexpected_keys == []
-        elif rank == 0:
-            print(f"WARNING: pretrained_backbone={backbone!r} is not a local file (no network): training from random init")
-    vit = vit.to(device)
-
-    optimizer_args = get_optimizer_args(train_config)
-    optimizer = create_optimizer(optimizer_args, vit)          # leaves out vit.unused_parameter_names() (det tokens unless live)
-    lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
+    vit, optimizer, lr_scheduler, optimizer_args = _model_and_optimizer(rank, config, data_config, device)
     weight_dict = {k: train_config[k] for k in _DET_WEIGHTS if k in train_config}     # an absent key is left out of the sum
     # "device_matcher": the assignment in HIP (mv_det_match) instead of scipy on the host; training and validation share it
     matcher = HungarianMatcher(assignment="device" if train_config.get("device_matcher", False) else "host")
     criterion = SetCriterion(data_config["number_of_classes"], matcher=matcher, weight_dict=weight_dict,
                              eos_coef=train_config["eos_coef"], losses=["labels", "boxes", "cardinality"]).to(device)
-    iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer,
-                                            lr_scheduler=lr_scheduler)
-    optimizer.arena.bump_versions()
-    reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())
-    broadcast_parameters(optimizer.arena)
-    _start_ema(optimizer)
-    optimizer.grad_scale = reducer.grad_scale
-    optimizer.max_grad_norm = optimizer_args.clip_grad         # the clip sequence of train_worker, see there
-    clip_every = optimizer_args.clip_grad is not None and n_batch_accum > 1
+    iteration, epoch_offset, window = _resume(train_config, vit, optimizer, lr_scheduler, optimizer_args.clip_grad, n_batch_accum,
+                                              batch_size * world, len(trainset), num_gpus)
+
+    def validate(suffix):                                      # on every rank, the EMA's too: the evaluator gathers
+        val_loss, ap, _ = detection_validation(coco_from_dataset(valset), val_loader, criterion, weight_dict, vit, verbose=(rank == 0))
+        return {"val_loss" + suffix: val_loss, "ap" + suffix: ap}
 
     vit.train()
     criterion.train()
-    epoch_offset = max(0, int(batch_size * world * iteration / max(len(trainset), 1)))
-    if num_gpus > 1:
-        dist.barrier()
-    n_accum, top_ap = 0, 0.0
+    top_ap = 0.0
     log = _JsonLines(os.path.join(out_dir, "train_log.jsonl")) if rank == 0 else None
     for epoch in range(epoch_offset, train_config["epochs"]):
         epoch_loss = 0.0
         if sampler is not None:
             sampler.set_epoch(epoch)
         for imgs, targets in train_loader:                     # every batch may have a new (H, W): no captured graph here
-            if n_accum == 0:
-                optimizer.zero_grad()
-            reducer.enabled = reducer.world > 1 and (clip_every or n_accum == n_batch_accum - 1)
             loss = _weighted(criterion(vit(imgs.tensors), targets), weight_dict)
-            loss.backward()
+            stepped = window.backward(loss)
             value = _loss_to_host(loss, criterion)
             epoch_loss += value / max(len(train_loader), 1)
-            n_accum += 1
-            if clip_every and n_accum < n_batch_accum:
-                reducer.finish()
-                optimizer.clip_accumulated()
-            if n_accum == n_batch_accum:
-                n_accum = 0
-                reducer.finish()
-                optimizer.step()
+            if stepped:
                 iteration += 1
                 if rank == 0:
                     print(f"Iteration {iteration}:\tloss={value:.4f}")
                     log.write(iteration=iteration, loss=value)
         if rank == 0:
             print(f"Epoch {epoch} validation...")
-        val_loss, ap, _ = detection_validation(coco_from_dataset(valset), val_loader, criterion, weight_dict, vit,
-                                               verbose=(rank == 0))
-        ema_row = {}
-        if _has_ema(optimizer):                                # every rank, like the plain validation: the evaluator gathers
-            with optimizer.ema_weights():
-                val_loss_ema, ap_ema, _ = detection_validation(coco_from_dataset(valset), val_loader, criterion, weight_dict, vit,
-                                                               verbose=(rank == 0))
-            ema_row = {"val_loss_ema": val_loss_ema, "ap_ema": ap_ema}
+        row, ema_row = _validate_twice(optimizer, validate)
+        val_loss, ap = row["val_loss"], row["ap"]
         if ap >= top_ap and rank == 0:
             save_checkpoint(model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler, iteration=iteration,
                             filepath=f"{out_dir}/vit_epoch{epoch}", model_ema=_ema_state(optimizer, vit))
         top_ap = max(top_ap, ap)
         lr_scheduler.step(epoch)
         if rank == 0:
-            log.write(epoch=epoch, loss=epoch_loss, val_loss=val_loss, ap=ap, lr=optimizer.param_groups[0]["lr"], **ema_row)
+            log.write(epoch=epoch, loss=epoch_loss, val_loss=val_loss, ap=ap, lr=optimizer.param_groups[0]["lr"], **(ema_row or {}))
             print(f"Epoch : {epoch + 1} - loss : {epoch_loss:.4f} - val_loss : {val_loss:.4f} - val_acc: {ap:.4f}\n")
     if num_gpus > 1:
         cleanup_distributed()

@@ -22,6 +22,7 @@ An extension beyond the reference: the optional ``train_config`` keys ``layer_de
 scale and a weight decay per TENSOR and a weight EMA, stepped with ONE launch over the whole arena (``mv_adamw_table``).  Without
 the keys ``create_optimizer`` builds the ``AdamW`` described above and none of that code runs.
 """
+import contextlib
 import math
 from typing import Iterable, List, Tuple
 
@@ -44,8 +45,7 @@ class ParamArena:
         nd = lambda n, p: p.ndim <= 1 or n.endswith(".bias")
         self.torch_groups = [[n for n, p in every if nd(n, p)], [n for n, p in every if not nd(n, p)]]
         dev = named[0][1].device
-        decay = [(n, p) for n, p in named if not (p.ndim <= 1 or n.endswith(".bias"))]
-        no_decay = [(n, p) for n, p in named if (p.ndim <= 1 or n.endswith(".bias"))]
+        decay, no_decay = [(n, p) for n, p in named if not nd(n, p)], [(n, p) for n, p in named if nd(n, p)]
         self.names: List[str] = [n for n, _ in decay + no_decay]
         self.params: List[torch.nn.Parameter] = [p for _, p in decay + no_decay]
         # each tensor starts on a 32-byte boundary: kernels can use 16-byte vector access on any slice of the fp32 arena AND
@@ -103,6 +103,7 @@ class ParamArena:
 
 class AdamW:
     """torch.optim.AdamW semantics on the fused HIP kernel over a ``ParamArena`` (one launch per decay group)."""
+    ema, ema_loaded = None, False        # no weight EMA here (``TableAdamW`` may keep one): the loops ask every optimizer
 
     def __init__(self, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
         self.arena = arena
@@ -168,12 +169,12 @@ class AdamW:
 
     @torch.no_grad()
     def step(self):
+        """The frame of every step: gradients into their slots, the count, the optional clip reduction, ``_launch``, versions."""
         self.arena.sync_grads()
         if self._hyper is None:
             self.step_count += 1
         elif not torch.cuda.is_current_stream_capturing():
             self.advance()                # inside a capture the replayer advances (utils/graph.py)
-        b1, b2 = self.defaults["betas"]
         a = self.arena
         coef = None
         if self.max_grad_norm is not None:
@@ -181,6 +182,12 @@ class AdamW:
             # hold zeros): one norm reduction, and the coefficient rides into the AdamW kernel as a device scalar
             self.last_grad_norm = ops.grad_norm_clip(a.flat_grad, self.max_grad_norm, self.grad_scale)
             coef = self.last_grad_norm[1:2]
+        self._launch(coef)
+        a.bump_versions()
+
+    def _launch(self, coef):
+        """One launch per non-empty group, the decay group first."""
+        a, (b1, b2) = self.arena, self.defaults["betas"]
         for g in self.param_groups:
             lo, hi = g["range"]
             if hi > lo:
@@ -188,7 +195,6 @@ class AdamW:
                                lr=g["lr"], beta1=b1, beta2=b2, eps=self.defaults["eps"],
                                weight_decay=g["weight_decay"], step=self.step_count, grad_scale=self.grad_scale,
                                clip_coef=coef, hyper=None if self._hyper is None else self._hyper[g["name"]])
-        a.bump_versions()
 
     # checkpoint format = torch.optim.AdamW.state_dict() of the optimizer the reference builds (classification/train.py:
     # 161-166, utils/models.py:113-126): ``state`` keyed by the parameter's index in timm's group order with a per-parameter
@@ -312,6 +318,22 @@ def _check_unit(key, value, hi_closed=True):
     return float(value)
 
 
+def check_table_options(names, layer_decay=None, no_weight_decay=None, ema_decay=None, ema_key="ema_decay"):
+    """The three optional keys, checked against the parameter names ``names`` -> (layer_decay, no_weight_decay as a tuple, ema_decay).
+    ``ema_key``: what the caller's user calls the EMA decay (``model_ema_decay`` in a train_config); each message names its key."""
+    if layer_decay is not None:
+        layer_decay = _check_unit("layer_decay", layer_decay)
+    if ema_decay is not None:
+        ema_decay = _check_unit(ema_key, ema_decay, hi_closed=False)
+    if no_weight_decay is not None:
+        if not isinstance(no_weight_decay, (list, tuple)) or not all(isinstance(n, str) for n in no_weight_decay):
+            raise ValueError(f"no_weight_decay must be a list of parameter names, got {no_weight_decay!r}")
+        for n in no_weight_decay:
+            if n not in names:
+                raise ValueError(f"no_weight_decay names {n!r}, which is not a parameter of the model")
+    return layer_decay, tuple(no_weight_decay or ()), ema_decay
+
+
 class TableAdamW(AdamW):
     """``AdamW`` with a learning-rate scale and a weight decay PER TENSOR and an optional weight EMA, stepped with ONE
     ``mv_adamw_table`` launch over the whole arena (an extension; the reference has none of the three).
@@ -327,19 +349,12 @@ class TableAdamW(AdamW):
     def __init__(self, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, layer_decay=None,
                  no_weight_decay=(), ema_decay=None):
         super().__init__(arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        self.layer_decay = None if layer_decay is None else _check_unit("layer_decay", layer_decay)
-        self.ema_decay = None if ema_decay is None else _check_unit("ema_decay", ema_decay, hi_closed=False)
-        if isinstance(no_weight_decay, str):
-            raise ValueError(f"no_weight_decay must be a list of parameter names, got the string {no_weight_decay!r}")
-        self.no_weight_decay = tuple(no_weight_decay)
-        known = set(arena.names) | set(arena.torch_groups[0]) | set(arena.torch_groups[1])
-        for n in self.no_weight_decay:
-            if n not in known:
-                raise ValueError(f"no_weight_decay names {n!r}, which is not a parameter of the model")
+        known = set(arena.names) | set(arena.torch_groups[0]) | set(arena.torch_groups[1])      # the ones the arena leaves out too
+        self.layer_decay, self.no_weight_decay, self.ema_decay = check_table_options(known, layer_decay, no_weight_decay, ema_decay)
         self.lr_scales = layer_scales(arena.names, self.layer_decay) if self.layer_decay is not None else [1.0] * len(arena.names)
         self._tables_wd = None
         self._refresh_tables()
-        self.ema, self.ema_loaded, self._in_ema = None, False, False
+        self._in_ema = False
         if self.ema_decay is not None:
             self.ema = torch.zeros_like(arena.flat_param)
             self.reset_ema()
@@ -376,22 +391,15 @@ class TableAdamW(AdamW):
             raise ValueError(f"the two param_groups carry different learning rates ({[g['lr'] for g in self.param_groups]}): the one "
                              "launch steps at ONE scheduled rate times each tensor's scale")
         self._refresh_tables()
-        self.arena.sync_grads()
-        if self._hyper is None:
-            self.step_count += 1
-        elif not torch.cuda.is_current_stream_capturing():
-            self.advance()                # inside a capture the replayer advances (utils/graph.py)
-        b1, b2 = self.defaults["betas"]
-        a = self.arena
-        coef = None
-        if self.max_grad_norm is not None:
-            self.last_grad_norm = ops.grad_norm_clip(a.flat_grad, self.max_grad_norm, self.grad_scale)
-            coef = self.last_grad_norm[1:2]
+        super().step()
+
+    def _launch(self, coef):
+        """ONE launch over the whole arena, at the first group's (= the one) scheduled rate."""
+        a, (b1, b2), g = self.arena, self.defaults["betas"], self.param_groups[0]
         ops.adamw_table_step(a.flat_param, a.flat_grad, self.exp_avg, self.exp_avg_sq, self.items, self.seg_lr_scale, self.seg_wd,
-                             lr=lr, beta1=b1, beta2=b2, eps=self.defaults["eps"], step=self.step_count, grad_scale=self.grad_scale,
-                             clip_coef=coef, hyper=None if self._hyper is None else self._hyper[self.param_groups[0]["name"]],
+                             lr=g["lr"], beta1=b1, beta2=b2, eps=self.defaults["eps"], step=self.step_count,
+                             grad_scale=self.grad_scale, clip_coef=coef, hyper=None if self._hyper is None else self._hyper[g["name"]],
                              ema=self.ema, ema_decay=self.ema_decay if self.ema is not None else 0.0)
-        a.bump_versions()
 
     # -- the weight EMA -------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -408,25 +416,21 @@ class TableAdamW(AdamW):
             self.ema.copy_(tmp)
         self.arena.bump_versions()
 
+    @contextlib.contextmanager
     def ema_weights(self):
         """``with optimizer.ema_weights(): validate(model)``: the parameters hold the EMA inside the block and the trained weights
         again after it (the two buffers exchange contents, bit for bit)."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def swapped():
-            if self.ema is None:
-                raise RuntimeError("ema_weights(): this optimizer was built without ema_decay")
-            if self._in_ema:
-                raise RuntimeError("ema_weights() does not nest")
+        if self.ema is None:
+            raise RuntimeError("ema_weights(): this optimizer was built without ema_decay")
+        if self._in_ema:
+            raise RuntimeError("ema_weights() does not nest")
+        self._swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
             self._swap_ema()
-            self._in_ema = True
-            try:
-                yield self
-            finally:
-                self._in_ema = False
-                self._swap_ema()
-        return swapped()
 
     def ema_state_dict(self, model):
         """The model's state dict (host tensors) with every arena parameter replaced by its EMA: a checkpoint's ``"model_ema"``."""
@@ -517,17 +521,7 @@ def create_optimizer(args, model, skip=None):
     # two launches and everything else are the reference optimizer's.  Checked before the arena takes over the parameters.
     layer_decay, ema_decay = getattr(args, "layer_decay", None), getattr(args, "model_ema_decay", None)
     no_weight_decay = getattr(args, "no_weight_decay", None)
-    if layer_decay is not None:
-        _check_unit("layer_decay", layer_decay)
-    if ema_decay is not None:
-        _check_unit("model_ema_decay", ema_decay, hi_closed=False)
-    if no_weight_decay is not None:
-        if not isinstance(no_weight_decay, (list, tuple)) or not all(isinstance(n, str) for n in no_weight_decay):
-            raise ValueError(f"no_weight_decay must be a list of parameter names, got {no_weight_decay!r}")
-        have = {n for n, _ in model.named_parameters()}
-        for n in no_weight_decay:
-            if n not in have:
-                raise ValueError(f"no_weight_decay names {n!r}, which is not a parameter of the model")
+    check_table_options({n for n, _ in model.named_parameters()}, layer_decay, no_weight_decay, ema_decay, ema_key="model_ema_decay")
     arena = ParamArena(model.named_parameters(), skip=skip)
     betas = tuple(args.opt_betas) if getattr(args, "opt_betas", None) else (0.9, 0.999)
     eps = args.opt_eps if getattr(args, "opt_eps", None) is not None else 1e-8

@@ -131,8 +131,9 @@ def test_absent_keys_build_the_plain_optimizer():
     assert args.layer_decay is None and args.no_weight_decay is None and args.model_ema_decay is None
     opt = create_optimizer(args, _vit("classification"))
     assert type(opt) is AdamW
-    for attr in ("items", "seg_lr_scale", "seg_wd", "ema", "lr_scales"):
+    for attr in ("items", "seg_lr_scale", "seg_wd", "lr_scales"):
         assert not hasattr(opt, attr), attr                                     # no table attributes in use
+    assert opt.ema is None and "ema" not in vars(opt)                           # no EMA buffer: only the class's "none" answer
     opt = create_optimizer(argparse.Namespace(opt="adamw", lr=1e-3, weight_decay=0.05), _vit("classification"))
     assert type(opt) is AdamW                                                   # a namespace from before the keys existed
 
