@@ -31,7 +31,6 @@ def _parameters():
 LN = dict(ldx=136, rows=5, dim=136, eps=1e-5)                # one workgroup's worth plus a ragged edge
 LN_BWD = dict(ldx=136, rows=5, dim=136, lddx=136, accumulate=0, workspace_bytes=BIG, dy_dtype=0)
 NT = dict(lda=256, ldb=256, ldc=64, M=64, N=64, K=256, ld_aux=64, aux_i=0, ld_out2=64, alpha=1.0)
-F8C = dict(lda_bytes=512, ldb_bytes=512, ldc=64, M=64, N=64, K=128, scale_exp=0, ld_aux=64)
 GELU = 1                                                     # MV_EPI_GELU: bf16 output only, checked before anything is launched
 F32 = dict(sa_m=64, sa_k=1, sa_b1=0, sa_b2=0, sb_k=64, sb_n=1, sb_b1=0, sb_b2=0, sc_m=64, sc_n=1, sc_b1=0, sc_b2=0, M=64, N=64, K=64,
            nb1=1, nb2=1, alpha=1.0, accumulate=0, ld_aux=64, aux_i=1, ld_out2=64)
@@ -46,7 +45,6 @@ CASES = [
     ("mv_split2_bf16_ex", SPLIT_EX, "op", 3, SHAPE),
     ("mv_split3_bf16", SPLIT, "role", 2, SHAPE),
     ("mv_split2_bf16", SPLIT, "role", 2, SHAPE),
-    ("mv_split_f8c", dict(ldx=136, ldo_bytes=4 * 136, rows=5, cols=136, exp_hi=0), "role", 2, SHAPE),
     ("mv_weight_split", dict(R=64, C=64), "nseg", 4, SHAPE),
     ("mv_layernorm_fwd_split", LN, "nseg", 4, UNSUPPORTED),
     ("mv_layernorm_bwd_split", LN_BWD, "nseg", 4, UNSUPPORTED),
@@ -70,13 +68,11 @@ CASES = [
     ("mv_dropout", dict(n=680, p=0.1, seed=1, offset=0), "dtype", 7, UNSUPPORTED),
     ("mv_gemm_nt_bf16", dict(NT, epilogue=GELU), "c_dtype", 7, UNSUPPORTED),
     ("mv_gemm_nt_bf16_scaled", dict(NT, epilogue=GELU), "c_dtype", 7, UNSUPPORTED),
-    ("mv_gemm_nt_f8c", dict(F8C, epilogue=0), "c_dtype", 7, UNSUPPORTED),
     ("mv_gemm_nt_i8", dict(NT, epilogue=0, q_scale=0.05, q_zero_point=128), "c_dtype", 7, UNSUPPORTED),
     ("mv_gemm_f32", F32, "epilogue", 99, UNSUPPORTED),
     ("mv_gemm_nt_bf16", dict(NT, c_dtype=1), "epilogue", 99, UNSUPPORTED),
     ("mv_gemm_nt_bf16_scaled", dict(NT, c_dtype=1), "epilogue", 99, UNSUPPORTED),
     ("mv_gemm_nt_f16", NT, "epilogue", 99, UNSUPPORTED),
-    ("mv_gemm_nt_f8c", dict(F8C, c_dtype=0), "epilogue", 99, UNSUPPORTED),
     ("mv_gemm_nt_i8", dict(NT, c_dtype=0, q_scale=0.05, q_zero_point=128), "epilogue", 99, UNSUPPORTED),
     ("mv_attention_fwd_dh", ATT, "dim_head", 64, UNSUPPORTED),
     ("mv_attention_bwd_dh", ATT, "dim_head", 64, UNSUPPORTED),
