@@ -645,6 +645,45 @@ int mv_adamw_table(float* p, const float* g, float* m, float* v, float* ema, con
                    const int32_t* item_seg, long n_items, const float* seg_lr_scale, const float* seg_wd, int n_seg,
                    const float* hyper, float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
                    float grad_scale, const float* clip_coef, float ema_decay, mv_stream_t stream);
+/* ---- optimizer family: timm create_optimizer 'sgd' / 'momentum' (-> torch.optim.SGD, nesterov on / off) and 'lamb' (-> timm's
+ * Lamb) on the work list of mv_adamw_table (an extension: every reference train_config says "adamw", classification/train.py:161-166).
+ * Items, segments, hyper, grad_scale, clip_coef and ema / ema_decay as in mv_adamw_table; elements in no item are neither read nor
+ * written; no atomics, bitwise reproducible.
+ * mv_sgd_table, ONE launch.  Per element, gr = g * grad_scale (* clip_coef[0]), wd = seg_wd[seg] (torch.optim.SGD, dampening 0):
+ *   d = gr + wd * p;  buf = momentum * buf + d;  d = nesterov ? d + momentum * buf : buf;  p -= lr * seg_lr_scale[seg] * d
+ * momentum == 0: d stays gr + wd * p and buf is neither read nor written (it may be null).  A zero buf makes the first step
+ * buf = d, as torch's first step does.  Of hyper only hyper[0], the rate, is read.
+ * Checks, in this order and before any launch: n_items < 0 or n_seg <= 0 -> MV_ERR_SHAPE; momentum outside [0, 1) or NaN, nesterov
+ * with momentum == 0, or ema non-null with ema_decay outside [0, 1) -> MV_ERR_UNSUPPORTED; n_items == 0 -> MV_OK, nothing launched;
+ * p / g null, buf null with momentum != 0, any of them or ema not 16-byte aligned, or a null table -> MV_ERR_ALIGN. */
+int mv_sgd_table(float* p, const float* g, float* buf, float* ema, const int64_t* item_off, const int32_t* item_len,
+                 const int32_t* item_seg, long n_items, const float* seg_lr_scale, const float* seg_wd, int n_seg,
+                 const float* hyper, float lr, float momentum, int nesterov, float grad_scale, const float* clip_coef,
+                 float ema_decay, mv_stream_t stream);
+/* mv_lamb_table, TWO launches on the stream.  timm's Lamb with bias correction on, always_adapt off and no trust clip (its global
+ * gradient clip is the caller's mv_grad_norm_clip, handed in as clip_coef):
+ *   m = beta1 * m + (1 - beta1) * gr;  v = beta2 * v + (1 - beta2) * gr * gr
+ *   u = (m / bias_corr1) / (sqrt(v) / sqrt(bias_corr2) + eps) + wd * p
+ *   trust = (wd != 0 && ||p|| > 0 && ||u|| > 0) ? ||p|| / ||u|| : 1          (norms over the element's TENSOR)
+ *   p -= lr * seg_lr_scale[seg] * trust * u
+ * Launch 1 writes m and v and leaves (sum p^2, sum u^2) of every item, two doubles, in workspace.  Launch 2 runs per item again:
+ * its workgroup adds the pairs of all items of the item's tensor in a fixed order (in double), forms trust, recomputes u from the new
+ * m, v and the unchanged p, and writes p (and ema).  No atomics, no memset, no word passed between workgroups of one launch: every
+ * item of a tensor sees the same bits of trust, and a tensor's result depends neither on the grid nor on the rest of the arena.
+ * Two more device tables say which items form a tensor: item_tensor[n_items], the tensor of each item, in [0, n_tensors), and
+ * tensor_range[2 * n_tensors] = (first item, item count) of each tensor; a tensor's items are consecutive.  The tables are trusted.
+ * workspace: mv_lamb_workspace_bytes(n_items) bytes (16 per item), 16-byte aligned, owned by the caller and kept between calls (a
+ * captured step replays on it); it needs no initialisation.
+ * Checks, in this order and before any launch: n_items < 0, n_seg <= 0, n_tensors < 0 or n_tensors == 0 with items -> MV_ERR_SHAPE;
+ * a beta outside [0, 1), or ema non-null with ema_decay outside [0, 1) -> MV_ERR_UNSUPPORTED; n_items == 0 -> MV_OK, nothing
+ * launched; p / g / m / v null, any of them or ema not 16-byte aligned, a null table, or workspace null, misaligned or too small
+ * -> MV_ERR_ALIGN. */
+size_t mv_lamb_workspace_bytes(long n_items);
+int mv_lamb_table(float* p, const float* g, float* m, float* v, float* ema, const int64_t* item_off, const int32_t* item_len,
+                  const int32_t* item_seg, const int32_t* item_tensor, long n_items, const int32_t* tensor_range, int n_tensors,
+                  const float* seg_lr_scale, const float* seg_wd, int n_seg, const float* hyper, float lr, float beta1, float beta2,
+                  float eps, float bias_corr1, float bias_corr2, float grad_scale, const float* clip_coef, float ema_decay,
+                  void* workspace, size_t workspace_bytes, mv_stream_t stream);
 /* ---- gradient clipping: torch.nn.utils.clip_grad_norm_(vit.parameters(), clip_grad), classification/train.py:265-270 ----
  * over the flat gradient array g[n]: out[0] = total_norm = ||g * grad_scale||_2, out[1] = min(1, max_norm / (total_norm + 1e-6)).
  * out stays on the device; pass out + 1 as mv_adamw's clip_coef (it multiplies every gradient there: no extra pass).

@@ -125,6 +125,9 @@ SIGNATURES = {
     "mv_adamw": ("pppp" "l" "ffffffff" "p" "p", _I),
     "mv_adamw_dev": ("pppp" "l" "p" "fffff" "p" "p", _I),
     "mv_adamw_table": ("ppppp" "ppp" "l" "pp" "i" "p" "fffffff" "p" "f" "p", _I),
+    "mv_sgd_table": ("pppp" "ppp" "l" "pp" "i" "p" "ff" "i" "f" "p" "f" "p", _I),
+    "mv_lamb_workspace_bytes": ("l", _Z),
+    "mv_lamb_table": ("ppppp" "pppp" "l" "pi" "pp" "i" "p" "fffffff" "p" "f" "pz" "p", _I),
     "mv_grad_norm_workspace_bytes": ("", _Z),
     "mv_grad_norm_clip": ("pl" "ff" "p" "pz" "p", _I),
     "mv_dropout": ("ppi" "l" "f" "QQ" "p", _I),

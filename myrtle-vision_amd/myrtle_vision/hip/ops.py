@@ -1873,6 +1873,62 @@ def adamw_table_step(p, g, m, v, items, seg_lr_scale, seg_wd, *, lr, beta1, beta
                                grad_scale, _p(clip_coef), float(ema_decay), _s()), "adamw_table", n=p.numel(), items=off.numel())
 
 
+def _check_table_args(op, arrays, items, seg_lr_scale, seg_wd):
+    """The argument checks ``adamw_table_step`` makes, for the other optimizers on the same work list."""
+    off, length, seg = items
+    if not (off.dtype == torch.int64 and length.dtype == torch.int32 and seg.dtype == torch.int32
+            and off.numel() == length.numel() == seg.numel()):
+        raise ValueError(f"{op}: items are (int64 offsets, int32 lengths, int32 segments) of one length")
+    present = [a for a in arrays if a is not None]
+    if any(a.dtype != torch.float32 or a.numel() != present[0].numel() for a in present):
+        raise ValueError(f"{op}: the parameter, gradient, state (and ema) arrays must be fp32 of one size")
+    if seg_lr_scale.dtype != torch.float32 or seg_wd.dtype != torch.float32 or seg_lr_scale.numel() != seg_wd.numel():
+        raise ValueError(f"{op}: seg_lr_scale and seg_wd are fp32 tables of one length")
+
+
+def sgd_table_step(p, g, buf, items, seg_lr_scale, seg_wd, *, lr, momentum, nesterov, grad_scale=1.0, clip_coef=None, hyper=None,
+                   ema=None, ema_decay=0.0):
+    """In-place SGD over a whole flat fp32 arena in ONE launch (``mv_sgd_table``; ``torch.optim.SGD`` with dampening 0).  ``items``,
+    ``seg_lr_scale`` / ``seg_wd``, ``clip_coef``, ``hyper`` (only its first entry, the rate, is read) and ``ema`` as in
+    ``adamw_table_step``.  ``buf``: the momentum buffer, shaped like ``p``; None with ``momentum == 0`` (nothing is read or written)."""
+    off, length, seg = items
+    require_cuda(p, g, buf, off, length, seg, seg_lr_scale, seg_wd, clip_coef, hyper, ema)
+    _check_table_args("sgd_table_step", (p, g, buf, ema), items, seg_lr_scale, seg_wd)
+    if (buf is None) != (momentum == 0):
+        raise ValueError("sgd_table_step: a momentum buffer goes with momentum != 0, and only with it")
+    check(lib().mv_sgd_table(_p(p), _p(g), _p(buf), _p(ema), _p(off), _p(length), _p(seg), off.numel(), _p(seg_lr_scale), _p(seg_wd),
+                             seg_wd.numel(), _p(hyper), 0.0 if hyper is not None else lr, momentum, int(bool(nesterov)), grad_scale,
+                             _p(clip_coef), float(ema_decay), _s()), "sgd_table", n=p.numel(), items=off.numel())
+
+
+def lamb_workspace(n_items, device):
+    """The per-item partial sums of ``lamb_table_step`` (two doubles per item): allocated ONCE by the optimizer that steps with it, so
+    that a captured step replays on the same memory.  Needs no initialisation."""
+    return torch.empty(max(1, lib().mv_lamb_workspace_bytes(int(n_items)) // 8), dtype=torch.float64, device=device)
+
+
+def lamb_table_step(p, g, m, v, items, item_tensor, tensor_range, seg_lr_scale, seg_wd, workspace, *, lr, beta1, beta2, eps, step,
+                    grad_scale=1.0, clip_coef=None, hyper=None, ema=None, ema_decay=0.0):
+    """In-place LAMB over a whole flat fp32 arena in TWO launches (``mv_lamb_table``): the moments and one pair of partial sums per
+    item, then per item the trust ratio ``||p|| / ||u||`` of its tensor and the step.  ``item_tensor`` (int32 [n_items]) and
+    ``tensor_range`` (int32 [n_tensors, 2]: first item, item count) from ``utils.optim.build_item_tensors``; ``workspace`` from
+    ``lamb_workspace``; everything else as in ``adamw_table_step``."""
+    off, length, seg = items
+    require_cuda(p, g, m, v, off, length, seg, item_tensor, tensor_range, seg_lr_scale, seg_wd, workspace, clip_coef, hyper, ema)
+    _check_table_args("lamb_table_step", (p, g, m, v, ema), items, seg_lr_scale, seg_wd)
+    if not (item_tensor.dtype == torch.int32 and item_tensor.numel() == off.numel() and tensor_range.dtype == torch.int32
+            and tensor_range.dim() == 2 and tensor_range.shape[1] == 2 and tensor_range.is_contiguous()):
+        raise ValueError("lamb_table_step: item_tensor is int32 [n_items], tensor_range int32 [n_tensors, 2]")
+    if workspace.dtype != torch.float64 or workspace.numel() < 2 * off.numel():
+        raise ValueError("lamb_table_step: the workspace holds two doubles per item (lamb_workspace)")
+    bc1, bc2 = (1.0, 1.0) if hyper is not None else (1.0 - beta1 ** step, 1.0 - beta2 ** step)
+    check(lib().mv_lamb_table(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(off), _p(length), _p(seg), _p(item_tensor), off.numel(),
+                              _p(tensor_range), tensor_range.shape[0], _p(seg_lr_scale), _p(seg_wd), seg_wd.numel(), _p(hyper),
+                              0.0 if hyper is not None else lr, beta1, beta2, eps, bc1, bc2, grad_scale, _p(clip_coef),
+                              float(ema_decay), _p(workspace), workspace.numel() * 8, _s()), "lamb_table", n=p.numel(),
+          items=off.numel())
+
+
 def grad_norm_clip(g, max_norm, grad_scale=1.0):
     """-> fp32 [2] on the device: (total_norm of g * grad_scale, min(1, max_norm / (total_norm + 1e-6))) -- the two numbers
     of torch.nn.utils.clip_grad_norm_ (classification/train.py:265-270); no host synchronisation."""

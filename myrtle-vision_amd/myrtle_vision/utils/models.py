@@ -81,6 +81,9 @@ def get_optimizer_args(train_config):
     a.layer_decay = train_config.get("layer_decay")
     a.no_weight_decay = train_config.get("no_weight_decay")
     a.model_ema_decay = train_config.get("model_ema_decay")
+    # "optimizer": "lamb" only (utils/optim.py TableLamb): the global gradient-norm clip timm's Lamb always makes; absent -> 1.0, its
+    # default; null switches it off
+    a.lamb_max_grad_norm = train_config.get("lamb_max_grad_norm", 1.0)
     return a
 
 

@@ -21,6 +21,13 @@ An extension beyond the reference: the optional ``train_config`` keys ``layer_de
 (timm's layer-wise learning-rate decay and ``no_weight_decay`` list, a model EMA) select ``TableAdamW`` below -- a learning-rate
 scale and a weight decay per TENSOR and a weight EMA, stepped with ONE launch over the whole arena (``mv_adamw_table``).  Without
 the keys ``create_optimizer`` builds the ``AdamW`` described above and none of that code runs.
+
+A second extension: ``"optimizer": "sgd"`` / ``"momentum"`` / ``"lamb"`` (timm's names; every reference config says ``"adamw"``) build
+``TableSGD`` and ``TableLamb`` on the same frame and the same work list (``csrc/optim_family.hip``).  ``TableSGD`` is
+``torch.optim.SGD`` with dampening 0, Nesterov for ``"sgd"`` and plain momentum for ``"momentum"`` as in timm, and is held to torch by
+the tests.  ``TableLamb`` restates timm's ``Lamb`` with bias correction on, ``always_adapt=False`` and ``trust_clip=False`` (PARITY
+UNPINNED, as above: timm is not available offline; the formulas in ``TableLamb``'s docstring are the definition, the tests hold the
+kernel to their fp64 evaluation).
 """
 import contextlib
 import math
@@ -104,6 +111,7 @@ class ParamArena:
 class AdamW:
     """torch.optim.AdamW semantics on the fused HIP kernel over a ``ParamArena`` (one launch per decay group)."""
     ema, ema_loaded = None, False        # no weight EMA here (``TableAdamW`` may keep one): the loops ask every optimizer
+    kind = "adamw"                       # what a checkpoint of this optimizer is; "adamw" is not written (the reference's format)
 
     def __init__(self, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
         self.arena = arena
@@ -113,13 +121,31 @@ class AdamW:
             dict(lr=lr, initial_lr=lr, weight_decay=weight_decay, range=(0, nd), name="decay"),
             dict(lr=lr, initial_lr=lr, weight_decay=0.0, range=(nd, arena.total), name="no_decay"),
         ]
-        self.exp_avg = torch.zeros_like(arena.flat_param)
-        self.exp_avg_sq = torch.zeros_like(arena.flat_param)
+        self._init_state()
         self.step_count = 0
         self.grad_scale = 1.0            # e.g. 1/world_size after a SUM all-reduce
         self.max_grad_norm = None        # train_config.clip_grad: clip_grad_norm_ folded into the step (train.py:265-270)
         self.last_grad_norm = None       # device tensor [total_norm, clip coefficient] of the last clipped step
         self._hyper = None               # use_device_scalars(): per-group fp32 [3] (lr, bias_corr1, bias_corr2) on the device
+
+    def _init_state(self):
+        """The state arrays, shaped like the arena (a subclass with other state allocates its own instead)."""
+        self.exp_avg = torch.zeros_like(self.arena.flat_param)
+        self.exp_avg_sq = torch.zeros_like(self.arena.flat_param)
+
+    def _bias_corrections(self):
+        """(1 - beta1^t, 1 - beta2^t) at the current step count."""
+        b1, b2 = self.defaults["betas"]
+        return 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count
+
+    def _clip_norm(self):
+        """The norm ``step()`` clips the gradient to, or None: ``train_config.clip_grad``."""
+        return self.max_grad_norm
+
+    def _check_kind(self, sd):
+        kind = sd.get("kind", "adamw")
+        if kind != self.kind:
+            raise ValueError(f"optimizer checkpoint was written by a {kind!r} optimizer, this one is {self.kind!r}")
 
     # -- per-step scalars on the device (HIP-graph capture: utils/graph.py) ---------------------------------------------
     def use_device_scalars(self, ring: int = 32):
@@ -136,8 +162,7 @@ class AdamW:
     def advance(self):
         """step_count += 1 and (lr, 1 - beta1^t, 1 - beta2^t) of every group -> the device, on the current stream."""
         self.step_count += 1
-        b1, b2 = self.defaults["betas"]
-        bc1, bc2 = 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count
+        bc1, bc2 = self._bias_corrections()
         i = self._stage_i
         self._stage_i = (i + 1) % len(self._stage)
         if self._stage_done[i] is not None:
@@ -176,11 +201,11 @@ class AdamW:
         elif not torch.cuda.is_current_stream_capturing():
             self.advance()                # inside a capture the replayer advances (utils/graph.py)
         a = self.arena
-        coef = None
-        if self.max_grad_norm is not None:
+        coef, max_norm = None, self._clip_norm()
+        if max_norm is not None:
             # torch.nn.utils.clip_grad_norm_ over every parameter that has a gradient = the whole arena (alignment gaps
             # hold zeros): one norm reduction, and the coefficient rides into the AdamW kernel as a device scalar
-            self.last_grad_norm = ops.grad_norm_clip(a.flat_grad, self.max_grad_norm, self.grad_scale)
+            self.last_grad_norm = ops.grad_norm_clip(a.flat_grad, max_norm, self.grad_scale)
             coef = self.last_grad_norm[1:2]
         self._launch(coef)
         a.bump_versions()
@@ -225,6 +250,7 @@ class AdamW:
         return {"state": state, "param_groups": groups, "param_names": names}
 
     def load_state_dict(self, sd):
+        self._check_kind(sd)
         a = self.arena
         index, names = self._torch_index()
         st = sd["state"]
@@ -307,6 +333,18 @@ def build_items(offsets, sizes, pairs):
             length.append(min(ITEM_MAX, n - k))
             seg.append(s)
     return off, length, seg, segments
+
+
+def build_item_tensors(sizes):
+    """Which items of ``build_items`` form a tensor (what LAMB's per-tensor norms need) -> (the tensor index of every item, every
+    tensor's first item, every tensor's item count).  Tensor t has ``ceil(sizes[t] / ITEM_MAX)`` consecutive items."""
+    item_tensor, first, count = [], [], []
+    for t, n in enumerate(sizes):
+        k = (n + ITEM_MAX - 1) // ITEM_MAX
+        first.append(len(item_tensor))
+        count.append(k)
+        item_tensor.extend([t] * k)
+    return item_tensor, first, count
 
 
 def _check_unit(key, value, hi_closed=True):
@@ -466,13 +504,162 @@ class TableAdamW(AdamW):
         return sd
 
     def load_state_dict(self, sd):
+        self._check_kind(sd)
+        self._check_recipe(sd)
+        super().load_state_dict(sd)
+        self._refresh_tables()
+
+    def _check_recipe(self, sd):
         if sd.get("layer_decay") != self.layer_decay:
             raise ValueError(f"optimizer checkpoint has layer_decay={sd.get('layer_decay')!r}, this optimizer {self.layer_decay!r}")
         if sorted(sd.get("no_weight_decay", ())) != sorted(self.no_weight_decay):
             raise ValueError(f"optimizer checkpoint has no_weight_decay={list(sd.get('no_weight_decay', ()))!r}, this optimizer "
                              f"{list(self.no_weight_decay)!r}")
-        super().load_state_dict(sd)
+
+
+class TableSGD(TableAdamW):
+    """``torch.optim.SGD`` (dampening 0) on ``TableAdamW``'s frame -- the step, the clip reduction, the device scalars, the EMA,
+    ``layer_decay`` and ``no_weight_decay`` are that class's -- stepped with ONE ``mv_sgd_table`` launch over the whole arena:
+
+        d = g + wd * p;  buf = momentum * buf + d;  d = nesterov ? d + momentum * buf : buf;  p -= lr * lr_scale * d
+
+    One state array, ``momentum_buffer``; with ``momentum == 0`` there is none and the kernel reads and writes no buffer.  A
+    checkpoint has the layout of the ``torch.optim.SGD`` timm would build (per-parameter ``momentum_buffer``, the two param groups)
+    plus ``kind``, ``step_count`` and ``TableAdamW``'s keys, which torch ignores."""
+    kind = "sgd"
+
+    def __init__(self, arena: ParamArena, lr=1e-3, momentum=0.9, nesterov=False, weight_decay=0.0, layer_decay=None,
+                 no_weight_decay=(), ema_decay=None):
+        self.momentum, self.nesterov = check_momentum(momentum, nesterov), bool(nesterov)
+        super().__init__(arena, lr=lr, weight_decay=weight_decay, layer_decay=layer_decay, no_weight_decay=no_weight_decay,
+                         ema_decay=ema_decay)
+        self.defaults = dict(lr=lr, momentum=self.momentum, nesterov=self.nesterov, weight_decay=weight_decay)
+
+    def _init_state(self):
+        self.momentum_buffer = torch.zeros_like(self.arena.flat_param) if self.momentum != 0 else None
+
+    def _bias_corrections(self):
+        return 1.0, 1.0                  # SGD has none; the kernel reads the rate only
+
+    def _launch(self, coef):
+        a, g = self.arena, self.param_groups[0]
+        ops.sgd_table_step(a.flat_param, a.flat_grad, self.momentum_buffer, self.items, self.seg_lr_scale, self.seg_wd, lr=g["lr"],
+                           momentum=self.momentum, nesterov=self.nesterov, grad_scale=self.grad_scale, clip_coef=coef,
+                           hyper=None if self._hyper is None else self._hyper[g["name"]], ema=self.ema,
+                           ema_decay=self.ema_decay if self.ema is not None else 0.0)
+
+    def state_dict(self):
+        a = self.arena
+        index, names = self._torch_index()
+        state = {}
+        if self.step_count > 0 and self.momentum_buffer is not None:
+            for n, p, o in zip(a.names, a.params, a.offsets):
+                state[index[n]] = {"momentum_buffer": self.momentum_buffer[o:o + p.numel()].view(p.shape).clone()}
+        by_name = {g["name"]: g for g in self.param_groups}
+        groups, first = [], 0
+        for gname, members in zip(("no_decay", "decay"), a.torch_groups):
+            g = by_name[gname]
+            groups.append({"lr": g["lr"], "momentum": self.momentum, "dampening": 0, "weight_decay": g["weight_decay"],
+                           "nesterov": self.nesterov, "maximize": False, "initial_lr": g["initial_lr"],
+                           "params": list(range(first, first + len(members)))})
+            first += len(members)
+        return {"state": state, "param_groups": groups, "param_names": names, "kind": self.kind, "step_count": self.step_count,
+                "layer_decay": self.layer_decay, "no_weight_decay": list(self.no_weight_decay)}
+
+    def load_state_dict(self, sd):
+        self._check_kind(sd)
+        self._check_recipe(sd)
+        a = self.arena
+        index, names = self._torch_index()
+        if "param_names" in sd and list(sd["param_names"]) != names:
+            raise ValueError("optimizer checkpoint was written for a different parameter list")
+        for n, p, o in zip(a.names, a.params, a.offsets):
+            ent = sd["state"].get(index[n])
+            if ent is None or ent.get("momentum_buffer") is None:
+                continue
+            if self.momentum_buffer is None:
+                raise ValueError("optimizer checkpoint carries momentum buffers, this optimizer has momentum 0")
+            if tuple(ent["momentum_buffer"].shape) != tuple(p.shape):
+                raise ValueError(f"optimizer state of {n}: shape {tuple(ent['momentum_buffer'].shape)} != {tuple(p.shape)}")
+            self.momentum_buffer[o:o + p.numel()].copy_(ent["momentum_buffer"].reshape(-1))
+        self.step_count = int(sd.get("step_count", 0))
+        by_name = {g["name"]: g for g in self.param_groups}
+        for gname, s in zip(("no_decay", "decay"), sd["param_groups"]):
+            by_name[gname].update({k: v for k, v in s.items() if k in ("lr", "initial_lr", "weight_decay")})
         self._refresh_tables()
+
+
+class TableLamb(TableAdamW):
+    """LAMB on ``TableAdamW``'s frame, state and checkpoint layout (``exp_avg``, ``exp_avg_sq``, the step count; plus ``kind``),
+    stepped with ``mv_lamb_table``: two launches over the whole arena and a per-tensor reduction between them that uses no atomics,
+    no memset and no host read.  With ``gr`` the gradient after the clip, ``bc1 = 1 - beta1^t``, ``bc2 = 1 - beta2^t``, per tensor:
+
+        m = beta1 * m + (1 - beta1) * gr;  v = beta2 * v + (1 - beta2) * gr * gr
+        u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd * p
+        trust = (wd != 0 and ||p|| > 0 and ||u|| > 0) ? ||p|| / ||u|| : 1
+        p = p - lr * lr_scale * trust * u
+
+    This is the arithmetic of timm's ``Lamb`` with bias correction on, ``always_adapt=False`` and ``trust_clip=False``, restated:
+    timm is not available offline, so the class is NOT pinned by parity to timm (PARITY UNPINNED, as the module docstring says of
+    the schedule); the formulas above are the definition and the tests hold the kernel to their fp64 evaluation.
+
+    timm's ``Lamb`` always clips the global gradient norm first (``max_grad_norm=1.0``): here ``lamb_max_grad_norm`` (None switches it
+    off), one ``ops.grad_norm_clip`` whose coefficient rides into the first launch.  With ``clip_grad`` (``max_grad_norm``) set as
+    well the step clips ONCE, to the smaller of the two: clipping to c and then to 1 is clipping to min(c, 1).  (The coefficient is
+    ``min(1, max_norm / (norm + 1e-6))``, ``clip_grad_norm_``'s; timm's own has no 1e-6.)"""
+    kind = "lamb"
+
+    def __init__(self, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, lamb_max_grad_norm=1.0,
+                 layer_decay=None, no_weight_decay=(), ema_decay=None):
+        self.lamb_max_grad_norm = check_lamb_max_grad_norm(lamb_max_grad_norm)
+        self.item_tensor = None
+        super().__init__(arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, layer_decay=layer_decay,
+                         no_weight_decay=no_weight_decay, ema_decay=ema_decay)
+
+    def _refresh_tables(self):
+        super()._refresh_tables()
+        if self.item_tensor is None:     # which items form a tensor, and the partial sums' home: sizes only, built ONCE
+            dev = self.arena.flat_param.device
+            item_tensor, first, count = build_item_tensors([p.numel() for p in self.arena.params])
+            self.item_tensor = torch.tensor(item_tensor, dtype=torch.int32, device=dev)
+            self.tensor_range = torch.tensor(list(zip(first, count)), dtype=torch.int32, device=dev).reshape(-1, 2)
+            self.workspace = ops.lamb_workspace(len(item_tensor), dev)
+
+    def _clip_norm(self):
+        norms = [n for n in (self.max_grad_norm, self.lamb_max_grad_norm) if n is not None]
+        return min(norms) if norms else None
+
+    def _launch(self, coef):
+        a, (b1, b2), g = self.arena, self.defaults["betas"], self.param_groups[0]
+        ops.lamb_table_step(a.flat_param, a.flat_grad, self.exp_avg, self.exp_avg_sq, self.items, self.item_tensor, self.tensor_range,
+                            self.seg_lr_scale, self.seg_wd, self.workspace, lr=g["lr"], beta1=b1, beta2=b2, eps=self.defaults["eps"],
+                            step=self.step_count, grad_scale=self.grad_scale, clip_coef=coef,
+                            hyper=None if self._hyper is None else self._hyper[g["name"]], ema=self.ema,
+                            ema_decay=self.ema_decay if self.ema is not None else 0.0)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["kind"] = self.kind
+        return sd
+
+
+def check_momentum(momentum, nesterov):
+    """``momentum``: a number in [0, 1), and not 0 with Nesterov (what torch.optim.SGD refuses too)."""
+    if not isinstance(momentum, (int, float)) or isinstance(momentum, bool) or not 0.0 <= momentum < 1.0:
+        raise ValueError(f"momentum must be a number in [0, 1), got {momentum!r}")
+    if nesterov and momentum == 0:
+        raise ValueError("\"optimizer\": \"sgd\" is Nesterov momentum (timm's meaning) and needs momentum > 0; \"momentum\" is the "
+                         "plain form")
+    return float(momentum)
+
+
+def check_lamb_max_grad_norm(value):
+    """``lamb_max_grad_norm``: a positive number, or None (no clip of LAMB's own)."""
+    if value is None:
+        return None
+    if not isinstance(value, (int, float)) or isinstance(value, bool) or not value > 0:
+        raise ValueError(f"lamb_max_grad_norm must be a positive number or null, got {value!r}")
+    return float(value)
 
 
 class CosineLRScheduler:
@@ -510,11 +697,15 @@ class CosineLRScheduler:
         self.__dict__.update(sd)
 
 
+OPTIMIZERS = ("adamw", "sgd", "momentum", "lamb")
+
+
 def create_optimizer(args, model, skip=None):
     """Counterpart of ``timm.optim.create_optimizer(args, model)`` for the options the reference configs use."""
     opt = str(args.opt).lower()
-    if opt != "adamw":
-        raise NotImplementedError(f"optimizer {args.opt!r}: only 'adamw' (every reference train_config) is implemented")
+    if opt not in OPTIMIZERS:
+        raise NotImplementedError(f"optimizer {args.opt!r}: implemented are {', '.join(repr(o) for o in OPTIMIZERS)} ('adamw' is "
+                                  "what every reference train_config uses)")
     if skip is None:
         skip = model.unused_parameter_names() if hasattr(model, "unused_parameter_names") else ()
     # optional train_config keys (an extension): any of them selects the one-launch TableAdamW; without them the object, its
@@ -522,8 +713,19 @@ def create_optimizer(args, model, skip=None):
     layer_decay, ema_decay = getattr(args, "layer_decay", None), getattr(args, "model_ema_decay", None)
     no_weight_decay = getattr(args, "no_weight_decay", None)
     check_table_options({n for n, _ in model.named_parameters()}, layer_decay, no_weight_decay, ema_decay, ema_key="model_ema_decay")
+    if opt in ("sgd", "momentum"):
+        check_momentum(args.momentum, opt == "sgd")
+    elif opt == "lamb":
+        check_lamb_max_grad_norm(getattr(args, "lamb_max_grad_norm", 1.0))
     arena = ParamArena(model.named_parameters(), skip=skip)
     betas = tuple(args.opt_betas) if getattr(args, "opt_betas", None) else (0.9, 0.999)
+    table = dict(layer_decay=layer_decay, no_weight_decay=no_weight_decay or (), ema_decay=ema_decay)
+    if opt in ("sgd", "momentum"):       # timm's meanings: "sgd" is Nesterov, "momentum" is not; both take args.momentum
+        return TableSGD(arena, lr=args.lr, momentum=args.momentum, nesterov=opt == "sgd", weight_decay=args.weight_decay, **table)
+    if opt == "lamb":
+        eps = args.opt_eps if getattr(args, "opt_eps", None) is not None else 1e-6
+        return TableLamb(arena, lr=args.lr, betas=betas, eps=eps, weight_decay=args.weight_decay,
+                         lamb_max_grad_norm=getattr(args, "lamb_max_grad_norm", 1.0), **table)
     eps = args.opt_eps if getattr(args, "opt_eps", None) is not None else 1e-8
     if layer_decay is None and ema_decay is None and no_weight_decay is None:
         return AdamW(arena, lr=args.lr, betas=betas, eps=eps, weight_decay=args.weight_decay)
