@@ -1,6 +1,7 @@
 // AdamW over the whole parameter arena in ONE launch, with a learning-rate scale and a weight decay per tensor and an optional
-// weight EMA (gfx950).  HBM-bound like adamw_kernel (elementwise.hip): 7 x 4 B per element, 9 x 4 B with the EMA.
-#include "mv_common.h"
+// weight EMA (gfx950).  HBM-bound like adamw_kernel (elementwise.hip): 7 x 4 B per element, 9 x 4 B with the EMA.  The work list, the
+// EMA line, the grid and the argument checks are those of optim_walk.h, shared with optim_family.hip; see the note at the kernel.
+#include "optim_walk.h"
 
 namespace {
 
@@ -22,9 +23,10 @@ __device__ __forceinline__ void adamw_table_one(float& P, float& M, float& V, fl
   P = __builtin_fmaf(keep, P, -q);                                              // p * (1 - lr * wd) - q
 }
 
-// Work items never cross a tensor: item it covers elements [item_off[it], item_off[it] + item_len[it]) of the arena, at most 4096
-// of them, starting 32-byte aligned, all of segment item_seg[it].  Workgroups stride over the items; the alignment gaps between
-// tensors are in no item, so nothing reads or writes them.  Every element has one owner: no atomics, the same bits on every run.
+// This kernel keeps its own copy of table_walk's frame (optim_walk.h) -- the item loop, the float4 body, the tail -- because it is the
+// one kernel of the work list whose speed the walk did not keep: through table_walk the launch with the EMA measured 0.2 to 0.4 %
+// slower in the median than this form, above the slowest run of this form (profiles/optim_walk.txt).  Written out, its machine code
+// is digest for digest what it was before the walk existed.  The EMA line, the grid and the argument checks are the shared ones.
 template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_table_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, float* __restrict__ ema,
@@ -61,7 +63,7 @@ __global__ __launch_bounds__(256) void adamw_table_kernel(float* __restrict__ p,
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         adamw_table_one(pp[e], mm[e], vv[e], gg[e], gscale, lr_eff, wd, b1, b2, eps, step, inv_sqrt_bc2);
-        if (EMA) ee[e] = __builtin_fmaf(d, ee[e], (1.f - d) * pp[e]);          // d * ema + (1 - d) * p_new, one form on both paths
+        if (EMA) table_ema(ee[e], pp[e], d);
       }
       reinterpret_cast<float4*>(ip)[i] = P;
       reinterpret_cast<float4*>(im)[i] = M;
@@ -73,20 +75,9 @@ __global__ __launch_bounds__(256) void adamw_table_kernel(float* __restrict__ p,
       float P = ip[i], M = im[i], V = iv[i];
       adamw_table_one(P, M, V, ig[i], gscale, lr_eff, wd, b1, b2, eps, step, inv_sqrt_bc2);
       ip[i] = P; im[i] = M; iv[i] = V;
-      if (EMA) ie[i] = __builtin_fmaf(d, ie[i], (1.f - d) * P);
+      if (EMA) table_ema(ie[i], P, d);
     }
   }
-}
-
-template <bool EMA>
-int adamw_table_launch(long n_items, hipStream_t s, float* p, const float* g, float* m, float* v, float* ema, const int64_t* item_off,
-                       const int32_t* item_len, const int32_t* item_seg, const float* seg_lr_scale, const float* seg_wd,
-                       const float* hyper, float lr, float b1, float b2, float eps, float bc1, float bc2, float gscale,
-                       const float* clip_coef, float d) {
-  const long resident = mv_resident_blocks<adamw_table_kernel<EMA>>(256, 0);
-  const int grid = (int)(n_items < resident ? n_items : resident);
-  return mv_launch<adamw_table_kernel<EMA>>(MV_HERE, grid, 256, 0, s, p, g, m, v, ema, item_off, item_len, item_seg, n_items,
-                                            seg_lr_scale, seg_wd, hyper, lr, b1, b2, eps, bc1, bc2, gscale, clip_coef, d);
 }
 
 }  // namespace
@@ -96,16 +87,13 @@ extern "C" int mv_adamw_table(float* p, const float* g, float* m, float* v, floa
                               const float* seg_wd, int n_seg, const float* hyper, float lr, float beta1, float beta2, float eps,
                               float bias_corr1, float bias_corr2, float grad_scale, const float* clip_coef, float ema_decay,
                               mv_stream_t stream) {
-  MV_REQUIRE(n_items >= 0 && n_seg > 0, MV_ERR_SHAPE);
-  MV_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, MV_ERR_UNSUPPORTED);      // a NaN fails every comparison
-  MV_REQUIRE(ema == nullptr || (ema_decay >= 0.f && ema_decay < 1.f), MV_ERR_UNSUPPORTED);
-  if (n_items == 0) return MV_OK;
-  MV_REQUIRE(p && g && m && v && mv_aligned16(p) && mv_aligned16(g) && mv_aligned16(m) && mv_aligned16(v) && mv_aligned16(ema),
-             MV_ERR_ALIGN);
-  MV_REQUIRE(item_off && item_len && item_seg && seg_lr_scale && seg_wd, MV_ERR_ALIGN);
-  if (ema)
-    return adamw_table_launch<true>(n_items, (hipStream_t)stream, p, g, m, v, ema, item_off, item_len, item_seg, seg_lr_scale, seg_wd,
-                                    hyper, lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, clip_coef, ema_decay);
-  return adamw_table_launch<false>(n_items, (hipStream_t)stream, p, g, m, v, nullptr, item_off, item_len, item_seg, seg_lr_scale,
-                                   seg_wd, hyper, lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, clip_coef, 0.f);
+  const table_list L{item_off, item_len, item_seg, n_items, seg_lr_scale, seg_wd};
+  const bool betas_ok = beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f;
+  if (int rc = table_check(L, n_seg, betas_ok, ema, ema_decay, {p, g, m, v}); rc != MV_OK || n_items == 0) return rc;
+  return mv_pick<0, 1>(ema != nullptr, [&](auto EMA) {
+    constexpr auto K = adamw_table_kernel<decltype(EMA)::value != 0>;
+    return mv_launch<K>(MV_HERE, table_grid<K>(n_items), 256, 0, (hipStream_t)stream, p, g, m, v, ema, item_off, item_len, item_seg, n_items,
+                        seg_lr_scale, seg_wd, hyper, lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, clip_coef,
+                        ema ? ema_decay : 0.f);
+  });
 }

@@ -1858,23 +1858,16 @@ def adamw_table_step(p, g, m, v, items, seg_lr_scale, seg_wd, *, lr, beta1, beta
     int32 [n], segments int32 [n]) on the device, cut by ``utils.optim.build_items``; ``seg_lr_scale`` / ``seg_wd`` fp32 [n_seg]:
     element i of an item of segment s steps at ``lr * seg_lr_scale[s]`` with weight decay ``seg_wd[s]``.  ``clip_coef`` and ``hyper``
     as in ``adamw_step``.  ``ema`` (fp32, shaped like ``p``): ``ema = ema_decay * ema + (1 - ema_decay) * p_new`` in the same pass."""
-    off, length, seg = items
-    require_cuda(p, g, m, v, off, length, seg, seg_lr_scale, seg_wd, clip_coef, hyper, ema)
-    if not (off.dtype == torch.int64 and length.dtype == torch.int32 and seg.dtype == torch.int32
-            and off.numel() == length.numel() == seg.numel()):
-        raise ValueError("adamw_table_step: items are (int64 offsets, int32 lengths, int32 segments) of one length")
-    if not (g.numel() == m.numel() == v.numel() == p.numel() and (ema is None or ema.numel() == p.numel())):
-        raise ValueError("adamw_table_step: p, g, m, v (and ema) must have one size")
-    if seg_lr_scale.dtype != torch.float32 or seg_wd.dtype != torch.float32 or seg_lr_scale.numel() != seg_wd.numel():
-        raise ValueError("adamw_table_step: seg_lr_scale and seg_wd are fp32 tables of one length")
-    bc1, bc2 = (1.0, 1.0) if hyper is not None else (1.0 - beta1 ** step, 1.0 - beta2 ** step)
-    check(lib().mv_adamw_table(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(off), _p(length), _p(seg), off.numel(), _p(seg_lr_scale),
-                               _p(seg_wd), seg_wd.numel(), _p(hyper), 0.0 if hyper is not None else lr, beta1, beta2, eps, bc1, bc2,
-                               grad_scale, _p(clip_coef), float(ema_decay), _s()), "adamw_table", n=p.numel(), items=off.numel())
+    require_cuda(p, g, m, v, *items, seg_lr_scale, seg_wd, clip_coef, hyper, ema)
+    item_ptrs, n_items, seg_args = _table_args("adamw_table_step", (p, g, m, v, ema), items, seg_lr_scale, seg_wd)
+    lr, bc1, bc2 = _launch_scalars(hyper, lr, (beta1, beta2), step)
+    check(lib().mv_adamw_table(_p(p), _p(g), _p(m), _p(v), _p(ema), *item_ptrs, n_items, *seg_args, _p(hyper), lr, beta1, beta2, eps,
+                               bc1, bc2, grad_scale, _p(clip_coef), float(ema_decay), _s()), "adamw_table", n=p.numel(), items=n_items)
 
 
-def _check_table_args(op, arrays, items, seg_lr_scale, seg_wd):
-    """The argument checks ``adamw_table_step`` makes, for the other optimizers on the same work list."""
+def _table_args(op, arrays, items, seg_lr_scale, seg_wd):
+    """The argument checks of every step on the work list, and the arguments they all pass -> (pointers to the item offsets, lengths
+    and segments), the item count, (pointers to ``seg_lr_scale`` and ``seg_wd``, the segment count)."""
     off, length, seg = items
     if not (off.dtype == torch.int64 and length.dtype == torch.int32 and seg.dtype == torch.int32
             and off.numel() == length.numel() == seg.numel()):
@@ -1884,6 +1877,12 @@ def _check_table_args(op, arrays, items, seg_lr_scale, seg_wd):
         raise ValueError(f"{op}: the parameter, gradient, state (and ema) arrays must be fp32 of one size")
     if seg_lr_scale.dtype != torch.float32 or seg_wd.dtype != torch.float32 or seg_lr_scale.numel() != seg_wd.numel():
         raise ValueError(f"{op}: seg_lr_scale and seg_wd are fp32 tables of one length")
+    return (_p(off), _p(length), _p(seg)), off.numel(), (_p(seg_lr_scale), _p(seg_wd), seg_wd.numel())
+
+
+def _launch_scalars(hyper, lr, betas=(0.0, 0.0), step=1):
+    """-> (lr, 1 - beta1^step, 1 - beta2^step) as launch arguments; 0.0 / 1.0 / 1.0 when ``hyper`` holds them on the device."""
+    return (0.0, 1.0, 1.0) if hyper is not None else (lr, 1.0 - betas[0] ** step, 1.0 - betas[1] ** step)
 
 
 def sgd_table_step(p, g, buf, items, seg_lr_scale, seg_wd, *, lr, momentum, nesterov, grad_scale=1.0, clip_coef=None, hyper=None,
@@ -1891,14 +1890,13 @@ def sgd_table_step(p, g, buf, items, seg_lr_scale, seg_wd, *, lr, momentum, nest
     """In-place SGD over a whole flat fp32 arena in ONE launch (``mv_sgd_table``; ``torch.optim.SGD`` with dampening 0).  ``items``,
     ``seg_lr_scale`` / ``seg_wd``, ``clip_coef``, ``hyper`` (only its first entry, the rate, is read) and ``ema`` as in
     ``adamw_table_step``.  ``buf``: the momentum buffer, shaped like ``p``; None with ``momentum == 0`` (nothing is read or written)."""
-    off, length, seg = items
-    require_cuda(p, g, buf, off, length, seg, seg_lr_scale, seg_wd, clip_coef, hyper, ema)
-    _check_table_args("sgd_table_step", (p, g, buf, ema), items, seg_lr_scale, seg_wd)
+    require_cuda(p, g, buf, *items, seg_lr_scale, seg_wd, clip_coef, hyper, ema)
+    item_ptrs, n_items, seg_args = _table_args("sgd_table_step", (p, g, buf, ema), items, seg_lr_scale, seg_wd)
     if (buf is None) != (momentum == 0):
         raise ValueError("sgd_table_step: a momentum buffer goes with momentum != 0, and only with it")
-    check(lib().mv_sgd_table(_p(p), _p(g), _p(buf), _p(ema), _p(off), _p(length), _p(seg), off.numel(), _p(seg_lr_scale), _p(seg_wd),
-                             seg_wd.numel(), _p(hyper), 0.0 if hyper is not None else lr, momentum, int(bool(nesterov)), grad_scale,
-                             _p(clip_coef), float(ema_decay), _s()), "sgd_table", n=p.numel(), items=off.numel())
+    check(lib().mv_sgd_table(_p(p), _p(g), _p(buf), _p(ema), *item_ptrs, n_items, *seg_args, _p(hyper), _launch_scalars(hyper, lr)[0],
+                             momentum, int(bool(nesterov)), grad_scale, _p(clip_coef), float(ema_decay), _s()), "sgd_table",
+          n=p.numel(), items=n_items)
 
 
 def lamb_workspace(n_items, device):
@@ -1913,20 +1911,17 @@ def lamb_table_step(p, g, m, v, items, item_tensor, tensor_range, seg_lr_scale, 
     item, then per item the trust ratio ``||p|| / ||u||`` of its tensor and the step.  ``item_tensor`` (int32 [n_items]) and
     ``tensor_range`` (int32 [n_tensors, 2]: first item, item count) from ``utils.optim.build_item_tensors``; ``workspace`` from
     ``lamb_workspace``; everything else as in ``adamw_table_step``."""
-    off, length, seg = items
-    require_cuda(p, g, m, v, off, length, seg, item_tensor, tensor_range, seg_lr_scale, seg_wd, workspace, clip_coef, hyper, ema)
-    _check_table_args("lamb_table_step", (p, g, m, v, ema), items, seg_lr_scale, seg_wd)
-    if not (item_tensor.dtype == torch.int32 and item_tensor.numel() == off.numel() and tensor_range.dtype == torch.int32
+    require_cuda(p, g, m, v, *items, item_tensor, tensor_range, seg_lr_scale, seg_wd, workspace, clip_coef, hyper, ema)
+    item_ptrs, n_items, seg_args = _table_args("lamb_table_step", (p, g, m, v, ema), items, seg_lr_scale, seg_wd)
+    if not (item_tensor.dtype == torch.int32 and item_tensor.numel() == n_items and tensor_range.dtype == torch.int32
             and tensor_range.dim() == 2 and tensor_range.shape[1] == 2 and tensor_range.is_contiguous()):
         raise ValueError("lamb_table_step: item_tensor is int32 [n_items], tensor_range int32 [n_tensors, 2]")
-    if workspace.dtype != torch.float64 or workspace.numel() < 2 * off.numel():
+    if workspace.dtype != torch.float64 or workspace.numel() < 2 * n_items:
         raise ValueError("lamb_table_step: the workspace holds two doubles per item (lamb_workspace)")
-    bc1, bc2 = (1.0, 1.0) if hyper is not None else (1.0 - beta1 ** step, 1.0 - beta2 ** step)
-    check(lib().mv_lamb_table(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(off), _p(length), _p(seg), _p(item_tensor), off.numel(),
-                              _p(tensor_range), tensor_range.shape[0], _p(seg_lr_scale), _p(seg_wd), seg_wd.numel(), _p(hyper),
-                              0.0 if hyper is not None else lr, beta1, beta2, eps, bc1, bc2, grad_scale, _p(clip_coef),
-                              float(ema_decay), _p(workspace), workspace.numel() * 8, _s()), "lamb_table", n=p.numel(),
-          items=off.numel())
+    lr, bc1, bc2 = _launch_scalars(hyper, lr, (beta1, beta2), step)
+    check(lib().mv_lamb_table(_p(p), _p(g), _p(m), _p(v), _p(ema), *item_ptrs, _p(item_tensor), n_items, _p(tensor_range),
+                              tensor_range.shape[0], *seg_args, _p(hyper), lr, beta1, beta2, eps, bc1, bc2, grad_scale, _p(clip_coef),
+                              float(ema_decay), _p(workspace), workspace.numel() * 8, _s()), "lamb_table", n=p.numel(), items=n_items)
 
 
 def grad_norm_clip(g, max_norm, grad_scale=1.0):

@@ -112,6 +112,10 @@ class AdamW:
     """torch.optim.AdamW semantics on the fused HIP kernel over a ``ParamArena`` (one launch per decay group)."""
     ema, ema_loaded = None, False        # no weight EMA here (``TableAdamW`` may keep one): the loops ask every optimizer
     kind = "adamw"                       # what a checkpoint of this optimizer is; "adamw" is not written (the reference's format)
+    state_names = ("exp_avg", "exp_avg_sq")      # the per-parameter state of a checkpoint: attributes shaped like the arena
+    step_in_state = True                 # torch.optim.AdamW keeps a ``step`` per parameter; else the checkpoint has one ``step_count``
+    optional_state = {}                  # state name -> the error when a checkpoint carries it and this optimizer keeps no such array;
+                                         # an entry may lack (or hold None for) these names only
 
     def __init__(self, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
         self.arena = arena
@@ -210,6 +214,14 @@ class AdamW:
         self._launch(coef)
         a.bump_versions()
 
+    def _shared_kw(self, coef, g, ema=False):
+        """The keywords every launch of group ``g`` is handed besides its own arithmetic: the gradient scale, the clip coefficient, the
+        group's scalars on the device (``use_device_scalars``) and, for a one-launch table step (``ema``), the weight EMA."""
+        kw = dict(grad_scale=self.grad_scale, clip_coef=coef, hyper=None if self._hyper is None else self._hyper[g["name"]])
+        if ema:
+            kw.update(ema=self.ema, ema_decay=self.ema_decay if self.ema is not None else 0.0)
+        return kw
+
     def _launch(self, coef):
         """One launch per non-empty group, the decay group first."""
         a, (b1, b2) = self.arena, self.defaults["betas"]
@@ -218,36 +230,43 @@ class AdamW:
             if hi > lo:
                 ops.adamw_step(a.flat_param[lo:hi], a.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
                                lr=g["lr"], beta1=b1, beta2=b2, eps=self.defaults["eps"],
-                               weight_decay=g["weight_decay"], step=self.step_count, grad_scale=self.grad_scale,
-                               clip_coef=coef, hyper=None if self._hyper is None else self._hyper[g["name"]])
+                               weight_decay=g["weight_decay"], step=self.step_count, **self._shared_kw(coef, g))
 
     # checkpoint format = torch.optim.AdamW.state_dict() of the optimizer the reference builds (classification/train.py:
     # 161-166, utils/models.py:113-126): ``state`` keyed by the parameter's index in timm's group order with a per-parameter
     # ``step``, ``param_groups`` = [no_decay, decay] carrying those indices.  ``param_names`` (index -> name) is an extra
-    # key torch ignores.  Parameters that never received a gradient (the detection tokens) have no state, as in torch.
+    # key torch ignores.  Parameters that never received a gradient (the detection tokens) have no state, as in torch.  A subclass
+    # says what differs: ``state_names``, ``optional_state``, ``step_in_state``, ``_group_fields`` and its ``kind``, written whenever it is not "adamw".
     def _torch_index(self):
         names = self.arena.torch_groups[0] + self.arena.torch_groups[1]
         return {n: i for i, n in enumerate(names)}, names
 
+    def _group_fields(self):
+        """What a torch param group of this optimizer carries besides lr, weight_decay, initial_lr and params."""
+        return {"betas": self.defaults["betas"], "eps": self.defaults["eps"], "amsgrad": False, "maximize": False}
+
     def state_dict(self):
         a = self.arena
         index, names = self._torch_index()
+        arrays = {k: getattr(self, k) for k in self.state_names if getattr(self, k) is not None}
         state = {}
-        if self.step_count > 0:
+        if self.step_count > 0 and arrays:
             for n, p, o in zip(a.names, a.params, a.offsets):
-                k = p.numel()
-                state[index[n]] = {"step": self.step_count,
-                                   "exp_avg": self.exp_avg[o:o + k].view(p.shape).clone(),
-                                   "exp_avg_sq": self.exp_avg_sq[o:o + k].view(p.shape).clone()}
+                state[index[n]] = {"step": self.step_count} if self.step_in_state else {}
+                state[index[n]].update({k: arr[o:o + p.numel()].view(p.shape).clone() for k, arr in arrays.items()})
         by_name = {g["name"]: g for g in self.param_groups}
         groups, first = [], 0
         for gname, members in zip(("no_decay", "decay"), a.torch_groups):
             g = by_name[gname]
-            groups.append({"lr": g["lr"], "betas": self.defaults["betas"], "eps": self.defaults["eps"],
-                           "weight_decay": g["weight_decay"], "amsgrad": False, "maximize": False,
-                           "initial_lr": g["initial_lr"], "params": list(range(first, first + len(members)))})
+            groups.append({"lr": g["lr"], **self._group_fields(), "weight_decay": g["weight_decay"], "initial_lr": g["initial_lr"],
+                           "params": list(range(first, first + len(members)))})
             first += len(members)
-        return {"state": state, "param_groups": groups, "param_names": names}
+        sd = {"state": state, "param_groups": groups, "param_names": names}
+        if self.kind != "adamw":
+            sd["kind"] = self.kind
+        if not self.step_in_state:
+            sd["step_count"] = self.step_count
+        return sd
 
     def load_state_dict(self, sd):
         self._check_kind(sd)
@@ -262,15 +281,20 @@ class AdamW:
             ent = st.get(n) if legacy else st.get(index[n])
             if ent is None:
                 continue
-            k = p.numel()
-            if tuple(ent["exp_avg"].shape) != tuple(p.shape):
-                raise ValueError(f"optimizer state of {n}: shape {tuple(ent['exp_avg'].shape)} != {tuple(p.shape)}")
-            self.exp_avg[o:o + k].copy_(ent["exp_avg"].reshape(-1))
-            self.exp_avg_sq[o:o + k].copy_(ent["exp_avg_sq"].reshape(-1))
+            for k in self.state_names:
+                if k in self.optional_state and ent.get(k) is None:
+                    continue
+                if getattr(self, k) is None:
+                    raise ValueError(self.optional_state[k])
+                if tuple(ent[k].shape) != tuple(p.shape):
+                    raise ValueError(f"optimizer state of {n}: shape {tuple(ent[k].shape)} != {tuple(p.shape)}")
+                getattr(self, k)[o:o + p.numel()].copy_(ent[k].reshape(-1))
             if "step" in ent:
                 steps.add(int(ent["step"]))
         if legacy:
             self.step_count = int(sd["step"])
+        elif not self.step_in_state:
+            self.step_count = int(sd.get("step_count", 0))
         else:
             if len(steps) > 1:
                 raise ValueError(f"per-parameter steps differ ({sorted(steps)}): one fused step counter cannot hold them")
@@ -436,8 +460,7 @@ class TableAdamW(AdamW):
         a, (b1, b2), g = self.arena, self.defaults["betas"], self.param_groups[0]
         ops.adamw_table_step(a.flat_param, a.flat_grad, self.exp_avg, self.exp_avg_sq, self.items, self.seg_lr_scale, self.seg_wd,
                              lr=g["lr"], beta1=b1, beta2=b2, eps=self.defaults["eps"], step=self.step_count,
-                             grad_scale=self.grad_scale, clip_coef=coef, hyper=None if self._hyper is None else self._hyper[g["name"]],
-                             ema=self.ema, ema_decay=self.ema_decay if self.ema is not None else 0.0)
+                             **self._shared_kw(coef, g, ema=True))
 
     # -- the weight EMA -------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -526,7 +549,8 @@ class TableSGD(TableAdamW):
     One state array, ``momentum_buffer``; with ``momentum == 0`` there is none and the kernel reads and writes no buffer.  A
     checkpoint has the layout of the ``torch.optim.SGD`` timm would build (per-parameter ``momentum_buffer``, the two param groups)
     plus ``kind``, ``step_count`` and ``TableAdamW``'s keys, which torch ignores."""
-    kind = "sgd"
+    kind, state_names, step_in_state = "sgd", ("momentum_buffer",), False
+    optional_state = {"momentum_buffer": "optimizer checkpoint carries momentum buffers, this optimizer has momentum 0"}
 
     def __init__(self, arena: ParamArena, lr=1e-3, momentum=0.9, nesterov=False, weight_decay=0.0, layer_decay=None,
                  no_weight_decay=(), ema_decay=None):
@@ -541,52 +565,13 @@ class TableSGD(TableAdamW):
     def _bias_corrections(self):
         return 1.0, 1.0                  # SGD has none; the kernel reads the rate only
 
+    def _group_fields(self):
+        return {"momentum": self.momentum, "dampening": 0, "nesterov": self.nesterov, "maximize": False}
+
     def _launch(self, coef):
         a, g = self.arena, self.param_groups[0]
         ops.sgd_table_step(a.flat_param, a.flat_grad, self.momentum_buffer, self.items, self.seg_lr_scale, self.seg_wd, lr=g["lr"],
-                           momentum=self.momentum, nesterov=self.nesterov, grad_scale=self.grad_scale, clip_coef=coef,
-                           hyper=None if self._hyper is None else self._hyper[g["name"]], ema=self.ema,
-                           ema_decay=self.ema_decay if self.ema is not None else 0.0)
-
-    def state_dict(self):
-        a = self.arena
-        index, names = self._torch_index()
-        state = {}
-        if self.step_count > 0 and self.momentum_buffer is not None:
-            for n, p, o in zip(a.names, a.params, a.offsets):
-                state[index[n]] = {"momentum_buffer": self.momentum_buffer[o:o + p.numel()].view(p.shape).clone()}
-        by_name = {g["name"]: g for g in self.param_groups}
-        groups, first = [], 0
-        for gname, members in zip(("no_decay", "decay"), a.torch_groups):
-            g = by_name[gname]
-            groups.append({"lr": g["lr"], "momentum": self.momentum, "dampening": 0, "weight_decay": g["weight_decay"],
-                           "nesterov": self.nesterov, "maximize": False, "initial_lr": g["initial_lr"],
-                           "params": list(range(first, first + len(members)))})
-            first += len(members)
-        return {"state": state, "param_groups": groups, "param_names": names, "kind": self.kind, "step_count": self.step_count,
-                "layer_decay": self.layer_decay, "no_weight_decay": list(self.no_weight_decay)}
-
-    def load_state_dict(self, sd):
-        self._check_kind(sd)
-        self._check_recipe(sd)
-        a = self.arena
-        index, names = self._torch_index()
-        if "param_names" in sd and list(sd["param_names"]) != names:
-            raise ValueError("optimizer checkpoint was written for a different parameter list")
-        for n, p, o in zip(a.names, a.params, a.offsets):
-            ent = sd["state"].get(index[n])
-            if ent is None or ent.get("momentum_buffer") is None:
-                continue
-            if self.momentum_buffer is None:
-                raise ValueError("optimizer checkpoint carries momentum buffers, this optimizer has momentum 0")
-            if tuple(ent["momentum_buffer"].shape) != tuple(p.shape):
-                raise ValueError(f"optimizer state of {n}: shape {tuple(ent['momentum_buffer'].shape)} != {tuple(p.shape)}")
-            self.momentum_buffer[o:o + p.numel()].copy_(ent["momentum_buffer"].reshape(-1))
-        self.step_count = int(sd.get("step_count", 0))
-        by_name = {g["name"]: g for g in self.param_groups}
-        for gname, s in zip(("no_decay", "decay"), sd["param_groups"]):
-            by_name[gname].update({k: v for k, v in s.items() if k in ("lr", "initial_lr", "weight_decay")})
-        self._refresh_tables()
+                           momentum=self.momentum, nesterov=self.nesterov, **self._shared_kw(coef, g, ema=True))
 
 
 class TableLamb(TableAdamW):
@@ -633,14 +618,7 @@ class TableLamb(TableAdamW):
         a, (b1, b2), g = self.arena, self.defaults["betas"], self.param_groups[0]
         ops.lamb_table_step(a.flat_param, a.flat_grad, self.exp_avg, self.exp_avg_sq, self.items, self.item_tensor, self.tensor_range,
                             self.seg_lr_scale, self.seg_wd, self.workspace, lr=g["lr"], beta1=b1, beta2=b2, eps=self.defaults["eps"],
-                            step=self.step_count, grad_scale=self.grad_scale, clip_coef=coef,
-                            hyper=None if self._hyper is None else self._hyper[g["name"]], ema=self.ema,
-                            ema_decay=self.ema_decay if self.ema is not None else 0.0)
-
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["kind"] = self.kind
-        return sd
+                            step=self.step_count, **self._shared_kw(coef, g, ema=True))
 
 
 def check_momentum(momentum, nesterov):
