@@ -698,6 +698,24 @@ int mv_grad_norm_clip(const float* g, long n, float grad_scale, float max_norm, 
  * (The reference draws its mask from torch's generator: same distribution, different stream -- parity is statistical.) */
 int mv_dropout(const void* x, void* y, int dtype, long n, float p, uint64_t seed, uint64_t offset, mv_stream_t stream);
 
+/* ---- stochastic depth ("drop path": timm's DropPath, scale_by_keep=True): one factor per sample and residual branch ----
+ * mv_drop_path_draw, ONE launch of one workgroup: table[r * B + b] = keep ? scale[r] : 0 for R branches and B samples, where
+ * keep = (word (e & 3) of Philox4x32-10(counter = (e >> 2, step), key = seed) >= thr[r]), e = r * B + b: mv_dropout's mask of
+ * R * B elements with offset = step.  state is a device uint64[2] = (seed, step), 16-byte aligned; after every read of it the
+ * kernel stores step + 1, so the next call (or the next replay of a captured call) draws the next table with no host value
+ * involved.  thr[R] = (uint32)(p_r * 2^32) and scale[R] = (float)(1 / (1 - p_r)) are the caller's, computed once in double.
+ * R * B <= 2^24 (MV_ERR_SHAPE beyond); R * B == 0 launches nothing and leaves state alone. */
+int mv_drop_path_draw(uint64_t* state, const uint32_t* thr, const float* scale, float* table, int R, int B, mv_stream_t stream);
+/* In place on f, both fp32 [B, per_sample], c fp32 [B]: f[b, :] = fmaf(c[b], f[b, :], x[b, :]) where c[b] != 0, and exactly
+ * x[b, :] where c[b] == 0 (f is then not read).  per_sample is arbitrary (a 16-byte vector that straddles samples takes one factor
+ * per element); x and f 16-byte aligned. */
+int mv_drop_path_add(const float* x, float* f, const float* c, int B, long per_sample, mv_stream_t stream);
+/* out[b, :] = round_to_out_dtype(c[b] * (float)in[b, :]): one rounding of the fp32 product; in and out fp32 or bf16 (MV_F32 /
+ * MV_BF16 as in_code / out_code, any pairing; MV_ERR_UNSUPPORTED otherwise), [B, per_sample], 16-byte aligned, not overlapping.  The backward of
+ * mv_drop_path_add with respect to f (in = the output gradient), and its own backward. */
+int mv_row_scale(const void* in, int in_code, void* out, int out_code, const float* c, int B, long per_sample,
+                 mv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // HBM-bound elementwise / layout kernels of the ViT hot path (gfx950).  All are grid-stride, 16 bytes per
 // lane where the layout allows it.
 #include "mv_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -756,18 +757,7 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
 
 // ---- dropout (nn.Dropout, vit.py:50,52,75,311): y = x * keep / (1 - p), keep ~ Bernoulli(1 - p) from Philox4x32-10.
 // Element i takes word i & 3 of the Philox block with counter (i >> 2, offset) and key seed: the mask is a pure function of
-// (seed, offset, i), so the backward regenerates it from the same two numbers instead of storing it.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
+// (seed, offset, i), so the backward regenerates it from the same two numbers instead of storing it (philox4x32_10: philox.h).
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long n, unsigned thr,
                                                       float scale, uint64_t seed, uint64_t offset) {

@@ -49,7 +49,8 @@ def _fwd(forward):
     def run(ctx, *args, **kwargs):
         # fused functions receive the model's precision as their last argument and follow it; granular ones (one reference
         # module each, no precision argument) follow the scope their caller opened (ViT.forward)
-        prec = args[-1] if args and isinstance(args[-1], str) else None
+        # (the block functions take one more argument after it, the optional per-sample scale: a tensor or None)
+        prec = next((a for a in reversed(args[-2:]) if isinstance(a, str)), None)
         ctx.mv_segments = ops.prec_segments(prec) if prec is not None else getattr(ops._seg_tls, "n", 6)
         with ops.segments(ctx.mv_segments):
             return forward(ctx, *args, **kwargs)
@@ -533,14 +534,72 @@ def chain_reset():
     _chain[0] = None
 
 
+# Stochastic depth (drop path) on the fused blocks: out[b] = x[b] + c[b] * f(LN(x[b])) with one factor c[b] per sample (``row_scale``,
+# fp32 [B]: 0 or 1 / (1 - p)).  Everything in a branch after its last non-linearity is linear, so the block keeps its fused path: the
+# last product runs without the residual and ``ops.drop_path_add`` finishes the row; in backward the branch's incoming gradient is
+# c * dout (``ops.row_scale``) and everything downstream of it is unchanged, while the residual gradient stays the unscaled dout:
+# dx = dout + LNbwd(J^T (c * dout)).  Two hand-offs between neighbouring blocks assume c == 1 and are switched off for such a block:
+# the forward link (``_chain_set(out, None)``: the next block's LayerNorm backward would write colsum(dout) into this block's
+# output-bias gradient, which is colsum(c * dout)) and the published side (bf16(dout) and colsum(dout), both unscaled).
+def _row_scale_arg(x, row_scale):
+    if row_scale.dtype != torch.float32 or row_scale.dim() != 1 or row_scale.shape[0] != x.shape[0] or row_scale.requires_grad:
+        raise ValueError(f"row_scale: expected an fp32 [{x.shape[0]}] tensor without gradient, got {tuple(row_scale.shape)} "
+                         f"{row_scale.dtype}")
+    ops.require_cuda(row_scale)
+    return _c(row_scale)
+
+
+def _drop_path_tail(a, M, K, weight, bias, out, D, x, row_scale):
+    """out = x + c * (a W^T + bias) on the bf16 and plain fp32 paths: the product into the fp32 ``out``, then the per-sample add."""
+    ops.linear_fwd(a, M, K, weight, bias, out, D, epi=EPI_NONE)
+    ops.drop_path_add(x, out, row_scale)
+
+
+def _side_or_none(ctx, dout, M, D, kind):
+    """``_take_side`` for a plain block; a drop-path block must not read the side (it is unscaled) and clears it."""
+    if ctx.row_scale is None:
+        return _take_side(dout, M, D, kind)
+    _side.clear()
+    return None, None
+
+
+def _branch_grad(ctx, dout, dtype):
+    """The gradient entering the branch, in ``dtype``: dout itself, or c * dout for a drop-path block."""
+    if ctx.row_scale is None:
+        return ops.cast(dout, dtype)
+    return ops.row_scale(dout, ctx.row_scale, dtype)
+
+
+class _DropPath(Function):
+    """y[b] * c[b] on the module-by-module path (timm's DropPath with the factors drawn elsewhere); same dtype out as in."""
+
+    @staticmethod
+    def forward(ctx, y, row_scale):
+        ops.require_cuda(y, row_scale)
+        ctx.save_for_backward(row_scale)
+        return ops.row_scale(_c(y), row_scale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (row_scale,) = ctx.saved_tensors
+        return ops.row_scale(_c(dy), row_scale), None
+
+
+def drop_path(y, row_scale):
+    """c[b] * y[b] for y [B, ...] (fp32 or bf16) and the per-sample factors ``row_scale`` (fp32 [B]); None = identity."""
+    if row_scale is None:
+        return y
+    return _DropPath.apply(y, _row_scale_arg(y, row_scale))
+
 
 class _AttnBlock(Function):
     """x + to_out(attention(to_qkv(LN(x))))  ==  Residual(PreNorm(dim, Attention)) (vit.py:131-141, 84-99)."""
 
     @staticmethod
     @_fwd
-    def forward(ctx, x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec):
+    def forward(ctx, x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec, row_scale=None):
         adt = ops.act_dtype(prec)
+        ctx.row_scale = row_scale
         B, T, D = x.shape
         M = B * T
         x = _c(x)
@@ -564,12 +623,16 @@ class _AttnBlock(Function):
             o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
             o6 = ops.split_ex(o.view(M, inner), M, inner)
             out = torch.empty_like(x)
-            ops.nt_x6(o6, wo, "fwd", M, out.view(M, D), bias=bo, residual=x.view(M, D))
+            if row_scale is None:
+                ops.nt_x6(o6, wo, "fwd", M, out.view(M, D), bias=bo, residual=x.view(M, D))
+            else:
+                ops.nt_x6(o6, wo, "fwd", M, out.view(M, D), bias=bo, residual=None)
+                ops.drop_path_add(x, out, row_scale)
             # the fused backward needs the attention output itself (delta = rowsum(dO * O)), not only its split
             ctx.save_for_backward(x, g, mean, rstd, y6, qkv, None if path == ops.ATTN_PROBS else o, o6, saved, wqkv, wo)
             ctx.cfg = (heads, scale)
             ctx.small = (b, bqkv, bo)
-            _chain_set(out, bo)
+            _chain_set(out, bo if row_scale is None else None)
             return out
         qkv = torch.empty(B, T, inner3, dtype=adt, device=x.device)
         ops.linear_fwd(y, M, D, wqkv, bqkv, qkv, inner3)
@@ -583,11 +646,14 @@ class _AttnBlock(Function):
         else:
             o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
         out = torch.empty_like(x)
-        ops.linear_fwd(o.view(M, inner), M, inner, wo, bo, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
+        if row_scale is None:
+            ops.linear_fwd(o.view(M, inner), M, inner, wo, bo, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
+        else:
+            _drop_path_tail(o.view(M, inner), M, inner, wo, bo, out, D, x, row_scale)
         ctx.save_for_backward(x, g, mean, rstd, y, qkv, o, None, saved, wqkv, wo)
         ctx.cfg = (heads, scale)
         ctx.small = (b, bqkv, bo)
-        _chain_set(out, bo)
+        _chain_set(out, bo if row_scale is None else None)
         return out
 
     @staticmethod
@@ -605,10 +671,10 @@ class _AttnBlock(Function):
         b, bqkv, bo = ctx.small
         dout = _c(dout)
         if ctx.x6:
-            d6, dbo = _take_side(dout, M, D, ("split", ops.current_segments()))   # the producing LayerNorm backward left both
+            d6, dbo = _side_or_none(ctx, dout, M, D, ("split", ops.current_segments()))   # the producing LayerNorm backward left both
             if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
                 dbo = ops.grad_out(bo, (D,), x.device)
-                d6 = ops.split_ex(dout.view(M, D), M, D, colsum_out=dbo)      # one pass: the split and the bias gradient
+                d6 = ops.split_ex(_branch_grad(ctx, dout, torch.float32).view(M, D), M, D, colsum_out=dbo)      # one pass: the split and the bias gradient
             dwo = ops.tn_x6(d6, o6, M, wo)
             do = torch.empty(B, T, inner, dtype=torch.float32, device=x.device)
             ops.nt_x6(d6, wo, "dx", M, do.view(M, inner))
@@ -625,11 +691,11 @@ class _AttnBlock(Function):
             dy = torch.empty(M, D, dtype=torch.float32, device=x.device)
             ops.nt_x6(dq6, wqkv, "dx", M, dy)
             dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, torch.float32, ctx.up_bias)
-            return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None
+            return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None, None
         adt = y.dtype
-        d_act, dbo = _take_side(dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
+        d_act, dbo = _side_or_none(ctx, dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
         if d_act is None:
-            d_act = ops.cast(dout, adt).view(M, D)                # dY of the projection, activation dtype
+            d_act = _branch_grad(ctx, dout, adt).view(M, D)       # dY of the projection, activation dtype
         # bf16: dW of to_out is computed below, with dW of to_qkv, in one grouped split-K launch (d_act and o stay alive)
         pair = adt == torch.bfloat16
         if not pair:
@@ -658,11 +724,14 @@ class _AttnBlock(Function):
         dy = torch.empty(M, D, dtype=adt, device=x.device)
         ops.linear_dx(dqkv.view(M, inner3), M, inner3, wqkv, dy, D)
         dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, adt, ctx.up_bias)   # + residual gradient
-        return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None
+        return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None, None
 
 
-def attn_block(x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec):
-    return _AttnBlock.apply(x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec)
+def attn_block(x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec, *, row_scale=None):
+    """``row_scale`` (fp32 [B] on the device, or None): the drop-path factors c of this branch, out[b] = x[b] + c[b] * f(LN(x[b]))."""
+    if row_scale is None:
+        return _AttnBlock.apply(x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec)
+    return _AttnBlock.apply(x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec, _row_scale_arg(x, row_scale))
 
 
 class _MlpBlock(Function):
@@ -670,8 +739,9 @@ class _MlpBlock(Function):
 
     @staticmethod
     @_fwd
-    def forward(ctx, x, g, b, w1, b1, w2, b2, prec):
+    def forward(ctx, x, g, b, w1, b1, w2, b2, prec, row_scale=None):
         adt = ops.act_dtype(prec)
+        ctx.row_scale = row_scale
         B, T, D = x.shape
         M = B * T
         Hd = w1.shape[0]
@@ -691,10 +761,14 @@ class _MlpBlock(Function):
                 ops.nt_x6(y6, w1, "fwd", M, h, bias=b1)
                 a6 = ops.split_ex(h, M, Hd, op=1)
             out = torch.empty_like(x)
-            ops.nt_x6(a6, w2, "fwd", M, out.view(M, D), bias=b2, residual=x.view(M, D))
+            if row_scale is None:
+                ops.nt_x6(a6, w2, "fwd", M, out.view(M, D), bias=b2, residual=x.view(M, D))
+            else:
+                ops.nt_x6(a6, w2, "fwd", M, out.view(M, D), bias=b2, residual=None)
+                ops.drop_path_add(x, out, row_scale)
             ctx.save_for_backward(x, g, mean, rstd, y6, h, a6, w1, w2)
             ctx.small = (b, b1, b2)
-            _chain_set(out, b2)
+            _chain_set(out, b2 if row_scale is None else None)
             return out
         # bf16: the fc1 epilogue leaves gelu'(pre-activation) for the backward pass (one multiply there instead of another
         # erf evaluation per element) -- as ONE BYTE per element (GELU_GRAD_BITS = 8: gelu' is confined to [-0.13, 1.13], a
@@ -706,10 +780,13 @@ class _MlpBlock(Function):
         ops.linear_fwd(y, M, D, w1, b1, a, Hd, epi=(EPI_GELU_GRAD8 if g8 else EPI_GELU_GRAD) if adt == torch.bfloat16 else EPI_GELU,
                        out2=h, ld_out2=Hd)
         out = torch.empty_like(x)
-        ops.linear_fwd(a, M, Hd, w2, b2, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
+        if row_scale is None:
+            ops.linear_fwd(a, M, Hd, w2, b2, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
+        else:
+            _drop_path_tail(a, M, Hd, w2, b2, out, D, x, row_scale)
         ctx.save_for_backward(x, g, mean, rstd, y, h, a, w1, w2)
         ctx.small = (b, b1, b2)
-        _chain_set(out, b2)
+        _chain_set(out, b2 if row_scale is None else None)
         return out
 
     @staticmethod
@@ -723,10 +800,10 @@ class _MlpBlock(Function):
             y6, a6 = y, a
             dout = _c(dout)
             b, b1, b2 = ctx.small
-            d6, db2 = _take_side(dout, M, D, ("split", ops.current_segments()))
+            d6, db2 = _side_or_none(ctx, dout, M, D, ("split", ops.current_segments()))
             if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
                 db2 = ops.grad_out(b2, (D,), x.device)
-                d6 = ops.split_ex(dout.view(M, D), M, D, colsum_out=db2)
+                d6 = ops.split_ex(_branch_grad(ctx, dout, torch.float32).view(M, D), M, D, colsum_out=db2)
             dw2 = ops.tn_x6(d6, a6, M, w2)
             db1 = ops.grad_out(b1, (Hd,), x.device)
             if ops.nt_split_ok(M, Hd, D):
@@ -739,12 +816,12 @@ class _MlpBlock(Function):
             dy = torch.empty(M, D, dtype=torch.float32, device=x.device)
             ops.nt_x6(dh6, w1, "dx", M, dy)
             dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, torch.float32, ctx.up_bias)
-            return dx, dg, db, dw1, db1, dw2, db2, None
+            return dx, dg, db, dw1, db1, dw2, db2, None, None
         adt = y.dtype
         dout = _c(dout)
-        d_act, db2 = _take_side(dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
+        d_act, db2 = _side_or_none(ctx, dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
         if d_act is None:
-            d_act = ops.cast(dout, adt).view(M, D)
+            d_act = _branch_grad(ctx, dout, adt).view(M, D)
         b, b1, b2 = ctx.small
         dw2, db2b = ops.linear_dw(d_act, a, M, D, Hd, want_bias=db2 is None, weight=w2, bias=b2)
         db2 = db2 if db2 is not None else db2b
@@ -762,11 +839,14 @@ class _MlpBlock(Function):
         dy = torch.empty(M, D, dtype=adt, device=x.device)
         ops.linear_dx(dh, M, Hd, w1, dy, D)
         dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, adt, ctx.up_bias)
-        return dx, dg, db, dw1, db1, dw2, db2, None
+        return dx, dg, db, dw1, db1, dw2, db2, None, None
 
 
-def mlp_block(x, g, b, w1, b1, w2, b2, prec):
-    return _MlpBlock.apply(x, g, b, w1, b1, w2, b2, prec)
+def mlp_block(x, g, b, w1, b1, w2, b2, prec, *, row_scale=None):
+    """``row_scale``: as in ``attn_block``."""
+    if row_scale is None:
+        return _MlpBlock.apply(x, g, b, w1, b1, w2, b2, prec)
+    return _MlpBlock.apply(x, g, b, w1, b1, w2, b2, prec, _row_scale_arg(x, row_scale))
 
 
 # ------------------------------------------------------------------------------------------------------------

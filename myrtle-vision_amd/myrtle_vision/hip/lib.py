@@ -131,6 +131,9 @@ SIGNATURES = {
     "mv_grad_norm_workspace_bytes": ("", _Z),
     "mv_grad_norm_clip": ("pl" "ff" "p" "pz" "p", _I),
     "mv_dropout": ("ppi" "l" "f" "QQ" "p", _I),
+    "mv_drop_path_draw": ("pppp" "ii" "p", _I),
+    "mv_drop_path_add": ("ppp" "il" "p", _I),
+    "mv_row_scale": ("pipip" "il" "p", _I),
 }
 
 _lock = threading.Lock()

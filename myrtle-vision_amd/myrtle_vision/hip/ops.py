@@ -1943,3 +1943,61 @@ def dropout(x, p, seed, offset, out=None):
     check(lib().mv_dropout(_p(x), _p(y), _DT[x.dtype], x.numel(), float(p), int(seed), int(offset), _s()), "dropout",
           n=x.numel(), p=p)
     return y
+
+
+# ------------------------------------------------------------------------------------------------------------
+# stochastic depth (drop path): one factor per sample and residual branch
+# ------------------------------------------------------------------------------------------------------------
+DROP_PATH_THREADS = 256           # threads per workgroup of mv_drop_path_add / mv_row_scale, one 16-byte vector each per grid pass
+DROP_PATH_MAX_BLOCKS_PER_CU = 8   # their grid never exceeds this many workgroups per compute unit (csrc/drop_path.hip)
+
+
+def drop_path_tables(rates):
+    """(thr, scale) of ``mv_drop_path_draw`` for drop rates ``rates`` (each in [0, 1)), computed in double on the host:
+    thr[r] = int(p_r * 2**32) as a python int, scale[r] = 1 / (1 - p_r) as a python float (the caller rounds it to fp32)."""
+    for p in rates:
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"drop path rate has to be in [0, 1), got {p}")
+    return [int(float(p) * 4294967296.0) for p in rates], [1.0 / (1.0 - float(p)) for p in rates]
+
+
+def drop_path_draw(state, thr, scale, B):
+    """One launch: a fresh fp32 [R, B] table of per-sample factors (0 or scale[r]) from the Philox stream of ``state`` (device
+    int64[2] = (seed, step)); the kernel leaves step + 1 in ``state``.  thr: device int32 [R] holding the uint32 thresholds."""
+    require_cuda(state, thr, scale)
+    R = thr.numel()
+    table = torch.empty(R, B, dtype=torch.float32, device=state.device)
+    check(lib().mv_drop_path_draw(_p(state), _p(thr), _p(scale), _p(table), R, B, _s()), "drop_path_draw", R=R, B=B)
+    return table
+
+
+def _row_scale_dims(t, c):
+    B = c.numel()
+    if t.shape[0] != B or not t.is_contiguous() or c.dtype != torch.float32 or not c.is_contiguous():
+        raise ValueError(f"per-sample scale: expected a contiguous [{B}, ...] tensor and a contiguous fp32 [{B}] scale, got "
+                         f"{tuple(t.shape)} and {tuple(c.shape)} {c.dtype}")
+    return B, t.numel() // B if B else 0
+
+
+def drop_path_add(x, f, c):
+    """In place on f (fp32, shaped like x): f[b] = x[b] + c[b] * f[b], exactly x[b] where c[b] == 0.  Returns f."""
+    require_cuda(x, f, c)
+    if x.dtype != torch.float32 or f.dtype != torch.float32 or x.shape != f.shape or not x.is_contiguous():
+        raise ValueError("drop_path_add: x and f are contiguous fp32 tensors of one shape")
+    B, per = _row_scale_dims(f, c)
+    check(lib().mv_drop_path_add(_p(x), _p(f), _p(c), B, per, _s()), "drop_path_add", B=B, per_sample=per)
+    return f
+
+
+def row_scale(x, c, out_dtype=None, out=None):
+    """c[b] * x[b] (fp32 product, rounded once) as a new tensor of ``out_dtype`` (default: x's), or into ``out`` (contiguous, x's
+    shape, not x itself); fp32 or bf16 either side."""
+    require_cuda(x, c, out)
+    out_dtype = (x.dtype if out_dtype is None else out_dtype) if out is None else out.dtype
+    B, per = _row_scale_dims(x, c)
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    elif out.shape != x.shape or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+        raise ValueError("row_scale: out is a contiguous tensor of x's shape, distinct from x")
+    check(lib().mv_row_scale(_p(x), _DT[x.dtype], _p(out), _DT[out_dtype], _p(c), B, per, _s()), "row_scale", B=B, per_sample=per)
+    return out

@@ -108,11 +108,17 @@ class Residual(nn.Module):
         self.fn = fn
         self.res_add = FloatFunctional()
 
-    def forward(self, x: torch.Tensor):
-        fused = self._fused(x)
+    def forward(self, x: torch.Tensor, row_scale: Optional[torch.Tensor] = None):
+        """``row_scale`` (extension, fp32 [B] on the device or None): the drop-path factors of this branch,
+        x + row_scale[b] * fn(x)[b] (``Transformer`` draws them)."""
+        if row_scale is not None:
+            inner = getattr(self.fn, "fn", None)
+            if type(inner) in (Attention, FeedForward) and inner.int8_pair() is not None:
+                raise ValueError("drop path applies in training: a converted int8 block is inference code and takes no row_scale")
+        fused = self._fused(x, row_scale)
         if fused is not None:
             return fused
-        return self.res_add.add(self.fn(x), x)
+        return self.res_add.add(F.drop_path(self.fn(x), row_scale), x)
 
     def _fusable_plain(self):
         """True when this is a plain Residual(PreNorm(FeedForward)) that nothing observes (no hooks, no quantiser stubs)."""
@@ -121,7 +127,7 @@ class Residual(nn.Module):
                 and not self._forward_pre_hooks and not pn._forward_hooks and not pn._forward_pre_hooks
                 and type(pn.fn) is FeedForward and pn.fn.fusable() and not pn.fn._forward_hooks and not pn.fn._forward_pre_hooks)
 
-    def _fused(self, x):
+    def _fused(self, x, row_scale=None):
         """One HIP-fused call for Residual(PreNorm(Attention | FeedForward)) when nothing observes the insides."""
         pn = self.fn
         if not (type(pn) is PreNorm and _plain(pn.norm, LayerNorm) and self.res_add.plain()):
@@ -135,10 +141,11 @@ class Residual(nn.Module):
         if type(inner) is Attention and inner.fusable():
             lin_o = inner.to_out[0]
             return F.attn_block(x, pn.norm.weight, pn.norm.bias, inner.to_qkv.weight, inner.to_qkv.bias, lin_o.weight,
-                                lin_o.bias, inner.heads, inner.scale, prec)
+                                lin_o.bias, inner.heads, inner.scale, prec, row_scale=row_scale)
         if type(inner) is FeedForward and inner.fusable():
             fc1, fc2 = inner.net[0], inner.net[3]
-            return F.mlp_block(x, pn.norm.weight, pn.norm.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, prec)
+            return F.mlp_block(x, pn.norm.weight, pn.norm.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, prec,
+                               row_scale=row_scale)
         # converted PyTorchINT8 blocks: the residual add rides in the second GEMM's epilogue, and without autograd every
         # quantiser is fused into the kernel that produces its input (int8_fused_forward)
         if type(inner) is Attention and inner.int8_pair() is not None:
@@ -300,9 +307,81 @@ class Attention(nn.Module):
 
 
 # ---- reference vit.py:102-161 -------------------------------------------------------------------------------
+def drop_path_rates(drop_path_rate: float, depth: int):
+    """Per-block drop rates, timm's rule: ``torch.linspace(0, drop_path_rate, depth)`` (block i: rate * i / (depth - 1); depth 1: 0)."""
+    rate = float(drop_path_rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path_rate has to be in [0, 1), got {drop_path_rate}")
+    return [rate * i / (depth - 1) if depth > 1 else 0.0 for i in range(depth)]
+
+
+class DropPathState:
+    """The draw of the drop-path factors of one ``Transformer``: a plain object, not a module -- no parameter, no buffer, no
+    state-dict key.  ``rates[r]`` is the drop rate of residual branch r of those that have one (> 0).  The device arrays --
+    ``state`` int64 [2] = (seed, step), ``thr`` (uint32 thresholds) and ``scale`` (fp32) [R] -- are created on the first training
+    forward.  ``draw`` is ONE launch (``mv_drop_path_draw``) that reads (seed, step) on the device, fills a fresh [R, B] table and
+    leaves step + 1 behind: no host read, no host scalar that changes, so a captured training step draws a new table on every replay.
+
+    The initial seed comes from torch's CPU generator, drawn with the first table as ``_Dropout`` draws its own (``seed_everything``
+    reproduces it; ``seed(int)`` sets it); the process's distributed rank is added when the arrays are created, because every rank is seeded alike and ranks must not share masks.  NOT checkpointed: a resumed
+    run draws a new seed.  The Philox stream is the project's own (``oracle/dropout_oracle.py`` with offset = step): same
+    distribution as timm's ``DropPath(scale_by_keep=True)``, different stream -- PARITY UNPINNED against timm."""
+
+    def __init__(self, rates):
+        self.rates = [float(p) for p in rates]
+        self.thr, self.scale = ops.drop_path_tables(self.rates)          # python ints / floats; device copies below
+        self._seed = None                # drawn with the first table, as _Dropout draws: building a model leaves the generator alone
+        self._step = 0
+        self._dev = None                                                 # (device, state, thr, scale)
+
+    def seed(self, seed: int, step: int = 0):
+        """Restart the stream at (seed + rank, step)."""
+        self._seed, self._step, self._dev = int(seed), int(step), None
+
+    @staticmethod
+    def _rank():
+        dist = torch.distributed
+        return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+    def arrays(self, device):
+        device = torch.device(device)
+        if self._dev is None or self._dev[0] != device:
+            import numpy as np
+            if self._dev is not None:                                    # the model moved: carry the stream over
+                self._seed, self._step = (int(v) for v in self._dev[1].tolist())
+                self._seed -= self._rank()
+            if self._seed is None:
+                self._seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+            state =torch.tensor([self._seed + self._rank(), self._step], dtype=torch.int64).to(device)
+            thr = torch.from_numpy(np.array(self.thr, dtype=np.uint32).view(np.int32)).to(device)
+            scale = torch.tensor(self.scale, dtype=torch.float64).to(torch.float32).to(device)
+            self._dev = (device, state, thr, scale)
+        return self._dev[1:]
+
+    @property
+    def state(self):
+        """Device int64 [2] = (seed, step), or None before the first training forward."""
+        return None if self._dev is None else self._dev[1]
+
+    def draw(self, B: int, device):
+        state, thr, scale = self.arrays(device)
+        return ops.drop_path_draw(state, thr, scale, B)
+
+
 class Transformer(nn.Module):
-    def __init__(self, dim: int, depth: int, heads: int, dim_head: int, mlp_dim: int, dropout: float, profile: bool):
+    def __init__(self, dim: int, depth: int, heads: int, dim_head: int, mlp_dim: int, dropout: float, profile: bool,
+                 drop_path_rate: float = 0.0):
         super().__init__()
+        # stochastic depth (an extension; timm's drop_path_rate): plain attributes only.  Both residual branches of block i use
+        # block_drop_rates[i]; branch (i, j) with a positive rate reads row drop_path_rows[(i, j)] of the table drawn per forward.
+        self.block_drop_rates = drop_path_rates(drop_path_rate, depth)
+        self.drop_path_rows = {}
+        for i, p in enumerate(self.block_drop_rates):
+            for j in (0, 1):
+                if p > 0.0:
+                    self.drop_path_rows[(i, j)] = len(self.drop_path_rows)
+        self.drop_path = DropPathState([self.block_drop_rates[i] for (i, _j) in self.drop_path_rows])   # in row order
+        self.last_table = None
         if profile:
             self.cm_attention = profiler.record_function("transformer:attention")
             self.cm_feedforward = profiler.record_function("transformer:feedforward")
@@ -332,13 +411,19 @@ class Transformer(nn.Module):
 
     def forward(self, x: torch.Tensor):
         last = len(self.layers) - 1
+        table = None
+        if self.training and self.drop_path_rows:
+            # ONE draw per forward into a fresh [R, B] table: a backward pass or a second micro-batch never reads an overwritten one
+            table = self.last_table = self.drop_path.draw(x.shape[0], x.device)
         for i, transformer_block in enumerate(self.layers):
+            # the branch's row of the table, if it has one; a branch without is called exactly as before
+            c = [() if table is None or (i, j) not in self.drop_path_rows else (table[self.drop_path_rows[(i, j)]],) for j in (0, 1)]
             with self.cm_attention:
-                x = transformer_block[0](x)
+                x = transformer_block[0](x, *c[0])
             with self.cm_feedforward:
                 if i == last and x.dim() == 3 and self._tail_prunable(transformer_block):
                     x = x[:, :1]                  # the slice's backward scatters the cls gradient into zeros for the other rows
-                x = transformer_block[1](x)
+                x = transformer_block[1](x, *c[1])
         return x
 
 
@@ -366,6 +451,7 @@ class ViT(nn.Module):
         precision: Optional[str] = None,
         prune_dead_tokens: Optional[bool] = None,
         live_det_tokens: bool = False,
+        drop_path_rate: float = 0.0,
     ):
         super().__init__()
         assert image_size % patch_size == 0, "Image dimensions must be divisible by the patch size."
@@ -409,7 +495,10 @@ class ViT(nn.Module):
         self.det_tokens = nn.Parameter(torch.randn(1, num_det_tokens, dim))
         self.dropout = Dropout(emb_dropout)
 
-        self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout, profile)
+        # Extension (off by default): stochastic depth, timm's ``drop_path_rate`` -- block i of ``depth`` drops each residual branch
+        # per sample with probability rate * i / (depth - 1) in training mode (``Transformer`` / ``DropPathState``); a ValueError
+        # outside [0, 1).  Plain attributes: state-dict keys and their order are those of a model without it.
+        self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout, profile, drop_path_rate=drop_path_rate)
         if prune_dead_tokens is None:
             prune_dead_tokens = os.environ.get("MYRTLE_VISION_PRUNE_DEAD_TOKENS", "0") == "1"
         self.transformer.cls_only_tail = bool(prune_dead_tokens) and decoder == "classification"

@@ -18,7 +18,8 @@ from myrtle_vision.utils.utils import parse_config
 
 
 def get_models(config, profile=False):
-    """reference utils/models.py:25-60 -> (vit, distiller=None).  Optional extension keys ``vit_config["precision"]`` and, for
+    """reference utils/models.py:25-60 -> (vit, distiller=None).  Optional extension keys ``vit_config["precision"]``,
+    ``vit_config["drop_path_rate"]`` (stochastic depth, ``ViT(drop_path_rate=...)``; absent = 0.0) and, for
     ``decoder: "detection"``, ``vit_config["live_det_tokens"]`` (ViT's opt-in YOLOS sequence assembly; the criterion, matcher and
     post-processing live in ``myrtle_vision.models.detector`` / ``.matcher``)."""
     vit_config = config["vit_config"]
@@ -42,6 +43,8 @@ def get_models(config, profile=False):
     }
     if vit_config.get("live_det_tokens"):
         vit_kwargs["live_det_tokens"] = True
+    if vit_config.get("drop_path_rate") is not None:
+        vit_kwargs["drop_path_rate"] = float(vit_config["drop_path_rate"])    # stochastic depth (an extension); absent -> 0.0
     if vit_config["decoder"] == "detection" and vit_config.get("num_det_tokens") is not None:
         vit_kwargs["num_det_tokens"] = vit_config["num_det_tokens"]    # the key the reference's yolos configs carry (default 100)
     return ViT(**vit_kwargs), None
