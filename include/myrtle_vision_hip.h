@@ -454,6 +454,36 @@ int mv_cross_entropy_soft(const float* logits, const int64_t* labels, float* los
 int mv_mix_batch(void* x, int elem, int B, int Ch, int H, int W, int mode, float lam, int y0, int y1, int x0, int x1,
                  mv_stream_t stream);
 
+/* ---- DeiT distillation loss (csrc/distill.hip): DistillWrapper.forward, models/distill.py:142-151 --
+ *   F.cross_entropy(student, labels) * alpha + F.kl_div(log_softmax(distill / T), softmax(teacher / T), "batchmean") * T^2 * (1 - alpha)
+ * -- with both gradients and the student's arg-max from one launch plus a one-wave fixed-order mean.
+ * student (class logits), distill (distillation-head logits), teacher: fp32 [B, C] dense; labels int64 [B].  Per sample:
+ *   CE_i = the per-sample value of mv_cross_entropy_soft on the student row (same lam, eps, pair_flip; lam = 1, eps = 0 is the
+ *          plain cross entropy), term for term;
+ *   mode MV_DISTILL_SOFT (0):  KD_i = T^2 * sum_c p_c (log p_c - log q_c), p = softmax(teacher_i / T), q = softmax(distill_i / T);
+ *          a class with p_c == 0 adds 0 (torch's kl_div);
+ *   mode MV_DISTILL_HARD (1):  KD_i = lse(distill_i) - distill_i[argmax_c teacher_i], first index wins, T unused (DeiT's
+ *          hard-label distillation; an extension, the reference has the soft form only).
+ * loss: fp32 [3] = (alpha * mean CE + (1 - alpha) * mean KD, mean CE, mean KD).  sample_loss: caller-provided fp32 [2 * B]
+ *   workspace, left holding CE_i in [0, B) and KD_i in [B, 2B); the means are one fixed-order reduction in a second one-wave
+ *   launch -- no floating-point atomics and no memset, so loss and gradients are bitwise reproducible run to run.  Nothing is read
+ *   back: the call can be captured in a graph.
+ * dstudent (optional, fp32 [B, C]) = alpha * (softmax(student_i) - target_i) * grad_scale / B;
+ * ddistill (optional, fp32 [B, C]) = (1 - alpha) * T * (q - p) * grad_scale / B (soft),
+ *                                    (1 - alpha) * (softmax(distill_i) - onehot(argmax teacher_i)) * grad_scale / B (hard);
+ *   a gradient whose weight is zero (alpha == 0, alpha == 1) is written as +0 throughout.  The teacher gets no gradient and is only read.
+ * argmax (optional, int64 [B]): arg-max of the student row, first index wins.
+ * A label outside [0, C), the sample's own or its partner's, is never used as an index: CE_i, the CE mean and the total are NaN
+ *   and its dstudent row is zero; KD_i and its ddistill row do not depend on the label.  One wave per sample: any C >= 2.
+ * MV_ERR_SHAPE: B < 0 or C < 2; MV_ERR_UNSUPPORTED: another mode, T <= 0 (or not finite), alpha outside [0, 1], eps outside
+ *   [0, 1), lam outside [0, 1], or pair_flip == 0 with lam != 1; MV_ERR_ALIGN: a null student / distill / teacher / labels / loss
+ *   / sample_loss.  B == 0: nothing is launched and no pointer is looked at, MV_OK. */
+#define MV_DISTILL_SOFT 0
+#define MV_DISTILL_HARD 1
+int mv_distill_loss(const float* student, const float* distill, const float* teacher, const int64_t* labels, float* loss,
+                    float* sample_loss, float* dstudent, float* ddistill, int64_t* argmax, int B, int C, int mode, float T,
+                    float alpha, float lam, float eps, int pair_flip, float grad_scale, mv_stream_t stream);
+
 /* ---- bilinear upsample (align_corners=False): nn.Upsample(size, 'bilinear') vit.py:355,371 ----
  * small[b, c, y, x] is read at  small + b*sb + c*sc + (y*w + x)*sp  (so the [B, h*w, C] output of the decoder GEMM is
  * consumed in place: the reference's transpose/view, vit.py:367-369, costs nothing); big: fp32 [B, C, H, W] dense.

@@ -15,6 +15,10 @@ seeding, batch-size solver, one process per GPU, rank-0 checkpoints every ``iter
 * ``clip_grad`` is the reference's ``clip_grad_norm_`` after EVERY micro-batch backward on the running accumulated gradient
   (classification/train.py:265-270): the intermediate clips rescale the gradient arena in place
   (``AdamW.clip_accumulated``), the last one rides into the AdamW kernel as a device scalar;
+* with a ``distiller_config`` (DeiT distillation, classification/train.py:162-163,238-253) the student runs ONCE per step -- the
+  training accuracy comes from the loss kernel's arg-max, where the reference runs the student a second time -- validation keeps the
+  plain criterion on the student's class logits (the reference validates the distiller's loss, train.py:41-42), and the checkpoint
+  gains a ``"distiller"`` entry (token and head; the reference drops them);
 * ``pretrained_backbone`` must be a local timm-format state dict (no network); a bare timm model NAME that is not a
   file means "random init" with a warning.
 
@@ -324,11 +328,35 @@ def _begin(rank, num_gpus, train_config, dist_config):
     return device, world, batch_size, n_batch_accum, out_dir
 
 
+_DISTILL_REFUSED_KEYS = ("layer_decay", "no_weight_decay", "model_ema_decay")
+
+
+def _check_distiller_config(config, task="classification"):
+    """A ``distiller_config`` beside a key it does not compose with yet: a ValueError that names the combination, before any device
+    work.  ``layer_decay`` / ``no_weight_decay`` go by parameter NAME and ``model_ema_decay`` keeps a model state dict; none of them
+    knows the ``student.`` prefix the parameters carry inside a ``DistillWrapper``.  The distillation token has no fake-quantiser
+    stub, so ``q_format`` must be ``"FP32"``."""
+    if "distiller_config" not in config:
+        return
+    if task != "classification":
+        raise ValueError(f"distiller_config is the classification recipe (DeiT distillation); task={task!r} does not take it")
+    for key in _DISTILL_REFUSED_KEYS:
+        if config["train_config"].get(key) is not None:
+            raise ValueError(f"train_config key {key!r} together with distiller_config is not supported: it goes by the plain model's "
+                             "parameter names, which carry a 'student.' prefix inside the distiller")
+    q_format = config["vit_config"].get("q_format", "FP32")
+    if q_format != "FP32":
+        raise ValueError(f"vit_config q_format={q_format!r} together with distiller_config is not supported: the distillation token "
+                         "has no fake-quantiser stub (use q_format 'FP32')")
+
+
 def _model_and_optimizer(rank, config, data_config, device):
     """After the loaders: the model (from a local ``pretrained_backbone`` if one is named) on the device, its optimizer and schedule
-    -> (vit, optimizer, lr_scheduler, optimizer_args)."""
+    -> (vit, optimizer, lr_scheduler, optimizer_args, distiller).  With a ``distiller_config`` the optimizer is built over the
+    ``DistillWrapper`` (classification/train.py:162-163): student, distillation token and head; the frozen teacher has no trainable
+    parameter and stays out of the arena, hence out of the gradient exchange and the parameter broadcast.  Else ``distiller`` is None."""
     train_config = config["train_config"]
-    vit, _ = get_models(config)
+    vit, distiller = get_models(config)
     backbone = train_config.get("pretrained_backbone")
     if backbone is not None:
         if isinstance(backbone, str) and os.path.exists(backbone):
@@ -338,10 +366,13 @@ def _model_and_optimizer(rank, config, data_config, device):
         elif rank == 0:
             print(f"WARNING: pretrained_backbone={backbone!r} is not a local file (no network): training from random init")
     vit = vit.to(device)
+    if distiller is not None:
+        distiller = distiller.to(device)                       # the student is the same module: moved once
     optimizer_args = get_optimizer_args(train_config)
-    optimizer = create_optimizer(optimizer_args, vit)          # leaves out vit.unused_parameter_names() (det tokens unless live)
+    # leaves out unused_parameter_names() (det tokens unless live) -- the model's, or the distiller's view of them
+    optimizer = create_optimizer(optimizer_args, vit if distiller is None else distiller)
     lr_scheduler, _ = create_scheduler(optimizer_args, optimizer)
-    return vit, optimizer, lr_scheduler, optimizer_args
+    return vit, optimizer, lr_scheduler, optimizer_args, distiller
 
 
 class AccumWindow:
@@ -383,10 +414,12 @@ class AccumWindow:
         return True
 
 
-def _resume(train_config, vit, optimizer, lr_scheduler, clip_grad, n_batch_accum, samples_per_iteration, n_train, num_gpus):
+def _resume(train_config, vit, optimizer, lr_scheduler, clip_grad, n_batch_accum, samples_per_iteration, n_train, num_gpus,
+            distiller=None):
     """After the criterion: the checkpoint (if any), the reducer, rank 0's parameters to every rank, the EMA's start, the clipping
     set-up; then every rank waits for the others -> (iteration, the epoch it falls in, the accumulation window)."""
-    iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler)
+    iteration = prepare_model_and_load_ckpt(train_config=train_config, model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler,
+                                            distiller=distiller)
     optimizer.arena.bump_versions()
     reducer = GradAllReducer(optimizer.arena, exchange_dtype=exchange_dtype_from_env())   # MV_DDP_EXCHANGE=bf16: half-width, opt-in
     broadcast_parameters(optimizer.arena)
@@ -425,10 +458,12 @@ def validation(val_loader, device, criterion, vit, task, num_classes):
 def train_worker(rank, num_gpus, config, task="classification"):
     if task == "detection":
         _seg_loss_spec(task, config["train_config"])           # the segmentation recipe key on this task: an error before any work
+        _check_distiller_config(config, task)
         return _train_detection(rank, num_gpus, config)
     train_config = config["train_config"]
     data_config = parse_config(config["data_config_path"])
     train_criterion, mixer = _train_criterion(task, train_config)      # first: a recipe key on the wrong task fails before any work
+    _check_distiller_config(config, task)
     seg_spec = _seg_loss_spec(task, train_config, data_config["number_of_classes"])
     device, world, batch_size, n_batch_accum, out_dir = _begin(rank, num_gpus, train_config, config["dist_config"])
 
@@ -443,11 +478,14 @@ def train_worker(rank, num_gpus, config, task="classification"):
     val_loader = BatchFeed(valset, plan_v, task, device, collate, batch_size=batch_size,
                            drop_last=train_config["drop_last_batch"])
 
-    vit, optimizer, lr_scheduler, optimizer_args = _model_and_optimizer(rank, config, data_config, device)
+    vit, optimizer, lr_scheduler, optimizer_args, distiller = _model_and_optimizer(rank, config, data_config, device)
     # validation keeps the plain criterion; without a recipe key it IS the training criterion, the reference's CrossEntropyLoss()
+    # (with a distiller too: the student's class logits against the labels, not the reference's distiller loss of
+    # classification/train.py:41-42, so that val_loss stays comparable between recipes -- and the teacher never runs in validation)
     criterion = train_criterion if type(train_criterion) is CrossEntropyLoss else CrossEntropyLoss()
     iteration, epoch_offset, window = _resume(train_config, vit, optimizer, lr_scheduler, optimizer_args.clip_grad, n_batch_accum,
-                                              batch_size * world, len(trainset), num_gpus)
+                                              batch_size * world, len(trainset), num_gpus, distiller=distiller)
+    smoothing = getattr(train_criterion, "smoothing", 0.0)     # SoftTargetCrossEntropy's; the plain criterion has none
     scalars = _Scalars(train_config.get("tensorboard_dir", "runs/")) if (task == "segmentation" and rank == 0) else None
     num_classes = data_config["number_of_classes"]
 
@@ -459,6 +497,8 @@ def train_worker(rank, num_gpus, config, task="classification"):
         return val
 
     vit.train()
+    if distiller is not None:
+        distiller.train()                                      # token and head; the teacher stays in eval mode
     last_val, last_val_ema = (0.0, 0.0, None), None
     for epoch in range(epoch_offset, train_config["epochs"]):
         epoch_loss = epoch_acc = 0.0
@@ -468,10 +508,18 @@ def train_worker(rank, num_gpus, config, task="classification"):
         for imgs, labels in train_loader:
             if iteration % train_config["iters_per_checkpoint"] == 0 and window.at_start and rank == 0:
                 save_checkpoint(model=vit, optimizer=optimizer, lr_scheduler=lr_scheduler, iteration=iteration,
-                                filepath=f"{out_dir}/vit_{iteration:06}", model_ema=_ema_state(optimizer, vit))
+                                filepath=f"{out_dir}/vit_{iteration:06}", model_ema=_ema_state(optimizer, vit), distiller=distiller)
             if iteration % train_config["iters_per_val"] == 0 and window.at_start and rank == 0:
                 last_val, last_val_ema = _validate_twice(optimizer, validate)    # the EMA's figures are logged beside the plain ones
-            if seg_spec is not None:                             # class weights / smoothing / Dice: the fused tail or an error
+            if distiller is not None:                            # DeiT distillation; the teacher sees the mixed batch, as in DeiT
+                lam = 1.0
+                if mixer is not None:
+                    imgs, lam = mixer(imgs, labels)
+                # ONE student pass: the arg-max for the accuracy comes from the loss kernel (the reference runs the student twice,
+                # classification/train.py:247-253)
+                loss, pred = distiller(imgs, labels, lam=lam, smoothing=smoothing, pair_flip=mixer is not None, return_argmax=True)
+                acc_t = (pred == labels).float().mean()
+            elif seg_spec is not None:                           # class weights / smoothing / Dice: the fused tail or an error
                 loss, acc_t, _, areas = vit.segmentation_loss(imgs, labels, loss=seg_spec, return_areas=True)
                 train_miou.add_areas(areas)                      # counted by the loss kernel: no second pass, no synchronisation
             elif _fused_seg_tail(task, criterion):
@@ -545,7 +593,7 @@ def evaluate(config, task, quantize=False, calib_steps=0, quantized_ckpt=False):
     q_format = vit_config["q_format"]
     if quantize and not quantized_ckpt:
         vit_config["q_format"] = "FP32"                                    # test_quantize.py:90-94: build FP32, load, then prepare
-    vit, _ = get_models(config)
+    vit, _ = get_models(config, with_teacher=False)            # a distillation run is evaluated on its student: no teacher file needed
     vit = vit.to("cuda")
     # "use_ema": true (top level or in train_config): evaluate the weight EMA the checkpoint carries under "model_ema"
     use_ema = bool(config.get("use_ema", train_config.get("use_ema", False)))
@@ -697,7 +745,7 @@ def _train_detection(rank, num_gpus, config):
     val_loader = BatchFeed(valset, plan_v, "detection", device, collate, sampler=val_sampler, batch_size=batch_size,
                            drop_last=train_config["drop_last_batch"])
 
-    vit, optimizer, lr_scheduler, optimizer_args = _model_and_optimizer(rank, config, data_config, device)
+    vit, optimizer, lr_scheduler, optimizer_args, _ = _model_and_optimizer(rank, config, data_config, device)
     weight_dict = {k: train_config[k] for k in _DET_WEIGHTS if k in train_config}     # an absent key is left out of the sum
     # "device_matcher": the assignment in HIP (mv_det_match) instead of scipy on the host; training and validation share it
     matcher = HungarianMatcher(assignment="device" if train_config.get("device_matcher", False) else "host")

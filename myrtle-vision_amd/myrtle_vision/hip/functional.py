@@ -853,20 +853,24 @@ def mlp_block(x, g, b, w1, b1, w2, b2, prec, *, row_scale=None):
 # decoders
 # ------------------------------------------------------------------------------------------------------------
 class _ClsHead(Function):
-    """ClassificationDecoder: linear(norm(x[:, 0])) (vit.py:335-342) -> fp32 logits [B, num_classes]."""
+    """ClassificationDecoder: linear(norm(x[:, row])) with row = 0 (vit.py:335-342) -> fp32 logits [B, num_classes]."""
 
     @staticmethod
     @_fwd
-    def forward(ctx, x, g, b, w, bias, prec):
+    def forward(ctx, x, g, b, w, bias, prec, row=0):
         adt = ops.act_dtype(prec)
         B, T, D = x.shape
         C = w.shape[0]
+        if not 0 <= row < T:
+            raise ValueError(f"cls_head: row {row} is outside the sequence of {T} tokens")
         x = _c(x)
-        y, mean, rstd = ops.layernorm_fwd(x, T * D, B, D, g, b, adt)        # rows = the cls tokens, T*D apart
+        # rows = token ``row`` of every image, T*D apart (row 0: the cls tokens)
+        y, mean, rstd = ops.layernorm_fwd(x if row == 0 else x.view(-1)[row * D:], T * D, B, D, g, b, adt)
         logits = torch.empty(B, C, dtype=torch.float32, device=x.device)
         ops.linear_fwd(y, B, D, w, bias, logits, C)
         ctx.save_for_backward(x, g, mean, rstd, y, w)
         ctx.small = (b, bias)
+        ctx.row = row
         return logits
 
     @staticmethod
@@ -884,12 +888,16 @@ class _ClsHead(Function):
         dy = torch.empty(B, D, dtype=adt, device=x.device)
         ops.linear_dx(dl, B, C, w, dy, D, ld_dy=ld)
         dx = torch.zeros_like(x)
-        dg, db = ops.layernorm_bwd(dy, x, T * D, g, mean, rstd, None, dx, T * D, B, D, beta=b)
-        return dx, dg, db, dw, dbias, None
+        o = ctx.row * D                                                    # the gradient goes to that row of every image
+        dg, db = ops.layernorm_bwd(dy, x if o == 0 else x.view(-1)[o:], T * D, g, mean, rstd, None,
+                                   dx if o == 0 else dx.view(-1)[o:], T * D, B, D, beta=b)
+        return dx, dg, db, dw, dbias, None, None
 
 
-def cls_head(x, g, b, w, bias, prec):
-    return _ClsHead.apply(x, g, b, w, bias, prec)
+def cls_head(x, g, b, w, bias, prec, row=0):
+    """``row`` (an extension): the token the head reads, 0 = the cls token (the reference's decoder); the distillation head of
+    ``models.distill`` reads the last one.  Only the base pointer of the LayerNorm moves: row 0 is the same launches and bits."""
+    return _ClsHead.apply(x, g, b, w, bias, prec, int(row))
 
 
 def _seg_small_fwd(x, g, b, w, bias, prec):
@@ -1171,6 +1179,44 @@ def det_append(x, det_tokens, pos_det):
     return _DetAppend.apply(x, det_tokens, pos_det)
 
 
+_neg_zero_rows = {}
+
+
+def _neg_zero_row(D, device):
+    """fp32 [1, D] of -0.0, kept on the device: the position row that makes ``mv_det_append_*`` a plain concatenation
+    (v + -0.0 is v bit for bit, for v = -0.0 and +0.0 too)."""
+    key = (torch.device(device), D)
+    if key not in _neg_zero_rows:
+        _neg_zero_rows[key] = torch.full((1, D), -0.0, dtype=torch.float32, device=device)
+    return _neg_zero_rows[key]
+
+
+class _TokenAppend(Function):
+    """cat(x, token) along the sequence (distill.py:65-69: the distillation token goes behind the positional add, so it has no
+    position row): ``mv_det_append_*`` with Q = 1.  Backward: dx = dout[:, :T0], dtoken = the batch-ordered sum of dout[:, T0]."""
+
+    @staticmethod
+    def forward(ctx, x, token):
+        ops.require_cuda(x, token)
+        D = x.shape[-1]
+        if token.numel() != D:
+            raise ValueError(f"token_append: a token of {D} elements expected, got {tuple(token.shape)}")
+        ctx.dims = (x.shape[1], token.shape)
+        ctx.param = token if token.is_leaf else None
+        return ops.det_append_fwd(_c(x.float()), ops._f32c(token).view(1, D), _neg_zero_row(D, x.device))
+
+    @staticmethod
+    def backward(ctx, dout):
+        T0, token_shape = ctx.dims
+        dx, dtoken, _ = ops.det_append_bwd(_c(dout.float()), T0, 1, ctx.param, None)
+        return dx, dtoken.view(token_shape)
+
+
+def token_append(x, token):
+    """x fp32 [B, T0, D], token [1, 1, D] (any shape of D elements) -> [B, T0 + 1, D] with the token as the last row of every image."""
+    return _TokenAppend.apply(x, token)
+
+
 class _DetSetLoss(Function):
     """SetCriterion's three differentiable scalars and two statistics (detector.py:41-98) from the per-query targets:
     -> (loss_ce, loss_bbox, loss_giou, class_error, cardinality_error), one kernel each way."""
@@ -1274,6 +1320,41 @@ class SoftTargetCrossEntropy(torch.nn.Module):
 
     def forward(self, logits, labels, lam=1.0):
         return soft_cross_entropy(logits, labels, lam, self.smoothing, True, self.return_argmax)
+
+
+class _DistillLoss(Function):
+    """DistillWrapper's loss (distill.py:142-151) with both gradients and the student's arg-max from one launch."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, student, distill, teacher, labels, temperature, alpha, mode, lam, smoothing, pair_flip):
+        ops.require_cuda(student, distill, teacher, labels)
+        loss, ds, dd, am, _ = ops.distill_loss(student.float(), distill.float(), teacher.detach().float(), labels, temperature, alpha,
+                                               mode, lam, smoothing, pair_flip, want_grad=True, want_argmax=True)
+        ctx.save_for_backward(ds, dd)
+        ctx.dtypes = (student.dtype, distill.dtype)
+        parts = loss.detach()[1:]
+        ctx.mark_non_differentiable(am, parts)
+        return loss[0].view(()), am, parts
+
+    @staticmethod
+    @_scoped
+    def backward(ctx, g, _g_argmax, _g_parts):
+        ds, dd = ctx.saved_tensors
+        return ((ds * g).to(ctx.dtypes[0]), (dd * g).to(ctx.dtypes[1])) + (None,) * 8
+
+
+def distill_loss(student, distill, teacher, labels, temperature=1.0, alpha=0.5, distillation_type="soft", lam=1.0, smoothing=0.0,
+                 pair_flip=False, return_argmax=False, return_parts=False):
+    """``alpha * CE(student, labels) + (1 - alpha) * KD(distill, teacher)`` (reference models/distill.py:142-151), KD = ``T^2 *
+    kl_div(log_softmax(distill / T), softmax(teacher / T), "batchmean")`` for ``distillation_type="soft"`` (the reference) or the
+    cross entropy against the teacher's arg-max for ``"hard"`` (DeiT's other variant).  The cross entropy is
+    ``soft_cross_entropy``'s (``lam``, ``smoothing``, ``pair_flip``; the defaults are the plain one).  The teacher gets no gradient.
+    ``return_argmax``: also the student's first-index arg-max (int64 [B]); ``return_parts``: also fp32 [2] = (CE mean, KD mean)."""
+    loss, am, parts = _DistillLoss.apply(student, distill, teacher, labels, float(temperature), float(alpha), str(distillation_type),
+                                         float(lam), float(smoothing), bool(pair_flip))
+    out = (loss,) + ((am,) if return_argmax else ()) + ((parts,) if return_parts else ())
+    return out if len(out) > 1 else loss
 
 
 # ------------------------------------------------------------------------------------------------------------

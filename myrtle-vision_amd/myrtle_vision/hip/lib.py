@@ -96,6 +96,7 @@ SIGNATURES = {
     "mv_cross_entropy": ("ppp" "pii" "p" "lil" "f" "p", _I),
     "mv_cross_entropy_soft": ("pppppp" "ii" "ff" "i" "f" "p", _I),
     "mv_mix_batch": ("pi" "iiii" "i" "f" "iiii" "p", _I),
+    "mv_distill_loss": ("ppppppppp" "iii" "ffff" "i" "f" "p", _I),
     "mv_upsample_bilinear_fwd": ("plll" "p" "iiiiii" "p", _I),
     "mv_upsample_bilinear_bwd": ("pplll" "iiiiii" "p", _I),
     "mv_gemm_force_variant": ("ii", _I),

@@ -1517,6 +1517,42 @@ def cross_entropy_soft(logits, labels, lam=1.0, smoothing=0.0, pair_flip=True, w
     return loss, dl, am, per_sample
 
 
+DISTILL_MODES = {"soft": 0, "hard": 1}          # MV_DISTILL_SOFT / MV_DISTILL_HARD
+
+
+def distill_loss(student, distill, teacher, labels, temperature=1.0, alpha=0.5, mode="soft", lam=1.0, smoothing=0.0,
+                 pair_flip=False, want_grad=False, want_argmax=False, grad_scale=1.0):
+    """DeiT distillation loss (mv_distill_loss; models/distill.py:142-151): ``alpha * CE(student, labels) + (1 - alpha) * KD`` with
+    ``KD = T^2 * kl_div(log_softmax(distill / T), softmax(teacher / T), "batchmean")`` (``mode="soft"``) or the cross entropy of the
+    distillation logits against the teacher's arg-max (``"hard"``).  All three logits fp32 [B, C], labels int64 [B]; the cross
+    entropy takes ``lam`` / ``smoothing`` / ``pair_flip`` as ``cross_entropy_soft`` does.  Host scalars throughout.
+    -> (loss [3] = total | CE mean | KD mean, dstudent|None, ddistill|None, argmax|None, per-sample losses [2, B])"""
+    require_cuda(student, distill, teacher, labels)
+    if mode not in DISTILL_MODES:
+        raise ValueError(f"distillation_type must be 'soft' or 'hard', got {mode!r}")
+    if student.dim() != 2 or distill.shape != student.shape or teacher.shape != student.shape or labels.shape != student.shape[:1]:
+        raise RuntimeError(f"distill_loss: three [B, C] logits and labels [B] expected, got {tuple(student.shape)}, "
+                           f"{tuple(distill.shape)}, {tuple(teacher.shape)} and {tuple(labels.shape)}")
+    if not (student.dtype == distill.dtype == teacher.dtype == torch.float32):
+        raise RuntimeError("distill_loss: fp32 logits expected")
+    student, distill, teacher, labels = student.contiguous(), distill.contiguous(), teacher.contiguous(), labels.contiguous()
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    B, C = student.shape
+    dev = student.device
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    per_sample = torch.empty(2, B, dtype=torch.float32, device=dev)
+    ds = torch.empty(B, C, dtype=torch.float32, device=dev) if want_grad else None
+    dd = torch.empty(B, C, dtype=torch.float32, device=dev) if want_grad else None
+    am = torch.empty(B, dtype=torch.int64, device=dev) if want_argmax else None
+    check(lib().mv_distill_loss(_p(student), _p(distill), _p(teacher), _p(labels), _p(loss), _p(per_sample), _p(ds), _p(dd), _p(am),
+                                B, C, DISTILL_MODES[mode], float(temperature), float(alpha), float(lam), float(smoothing),
+                                int(bool(pair_flip)), float(grad_scale), _s()),
+          "distill_loss", B=B, C=C, mode=mode, temperature=temperature, alpha=alpha, lam=lam, smoothing=smoothing,
+          pair_flip=bool(pair_flip))
+    return loss, ds, dd, am, per_sample
+
+
 def mix_batch(x, *, lam=None, box=None):
     """Mixup (``lam``) or CutMix (``box`` = (y0, y1, x0, x1)) of a dense [B, Ch, H, W] fp32 / bf16 batch IN PLACE
     (mv_mix_batch): sample i with sample B-1-i.  Both arguments are host scalars.  -> x"""

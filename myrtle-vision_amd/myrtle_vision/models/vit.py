@@ -625,7 +625,9 @@ class ViT(nn.Module):
         pred = logits.detach().argmax(dim=1)
         return loss, (pred == labels).float().mean(), pred.to(torch.uint8)
 
-    def _backbone(self, img: torch.Tensor):
+    def _backbone(self, img: torch.Tensor, extra_token: Optional[torch.Tensor] = None):
+        """``extra_token`` ([1, 1, D], ``models.distill``): appended as the last row of the sequence behind the positional add
+        (reference distill.py:65-69); None is the plain ViT, launch for launch."""
         ops.require_cuda(img, self.pos_embedding)
         F.chain_reset()                       # no stale producer link from an earlier pass or a stand-alone block call
         b_dim, c_dim, h_dim, w_dim = img.shape
@@ -640,6 +642,8 @@ class ViT(nn.Module):
             x = self._embed_unfused(img, gh, gw)
         if self.live_det_tokens:
             x = F.det_append(x, self.quant_det_tokens(self.det_tokens), self.pos_embedding_det)
+        if extra_token is not None:
+            x = F.token_append(x, extra_token)
         x = self.dropout(x)
 
         with self.cm_transformer:

@@ -31,6 +31,9 @@ class GraphedTrainStep:
     output (read it before the next call, or ``.clone()`` it)."""
 
     def __init__(self, model, optimizer, loss_fn, example_inputs, example_labels, warmup: int = 3):
+        if any(type(m).__name__ == "DistillWrapper" for m in model.modules()):
+            raise ValueError("GraphedTrainStep with a DistillWrapper (distiller_config) is not supported: a captured step with a frozen "
+                             "teacher pass in it has not been verified (a follow-up)")
         if not example_inputs.is_cuda:
             raise RuntimeError("GraphedTrainStep needs device tensors (the HIP path has no CPU fallback)")
         for m in model.modules():
