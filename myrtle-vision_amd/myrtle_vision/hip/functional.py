@@ -10,6 +10,10 @@ is called on its own).  The fused functions ``attn_block`` / ``mlp_block`` imple
     backward  :  dX GEMMs (fc2's with the GELU' epilogue), dW GEMMs (transposed LDS reads, split-K),
                  attention backward, LN backward with the residual gradient folded in.
 
+Both blocks stand in one frame, written once: ``_block_open`` (up to the LayerNorm forward), ``_block_close`` (the closing product,
+residual or drop-path add, the link to the next block), ``_block_grad_in`` (the incoming gradient) and ``_block_ln_bwd``.
+``_AttnBlock`` / ``_MlpBlock`` hold only what lies between, once per arithmetic (split-operand or plain).
+
 The residual stream and all gradients w.r.t. parameters are fp32; activations are bf16 (``prec='bf16'``) or fp32
 (``prec='fp32'``: parity mode, fp32-accurate arithmetic).  Backward runs on autograd's worker thread: everything here is stateless
 apart from caches keyed by tensor identity.
@@ -540,7 +544,9 @@ def chain_reset():
 # c * dout (``ops.row_scale``) and everything downstream of it is unchanged, while the residual gradient stays the unscaled dout:
 # dx = dout + LNbwd(J^T (c * dout)).  Two hand-offs between neighbouring blocks assume c == 1 and are switched off for such a block:
 # the forward link (``_chain_set(out, None)``: the next block's LayerNorm backward would write colsum(dout) into this block's
-# output-bias gradient, which is colsum(c * dout)) and the published side (bf16(dout) and colsum(dout), both unscaled).
+# output-bias gradient, which is colsum(c * dout)) and the published side (bf16(dout) and colsum(dout), both unscaled).  All of it
+# lives in the frame below: ``_block_close`` (the product without the residual, the add, no link) and ``_block_grad_in`` (c * dout,
+# no side); a block function never looks at ``row_scale``.
 def _row_scale_arg(x, row_scale):
     if row_scale.dtype != torch.float32 or row_scale.dim() != 1 or row_scale.shape[0] != x.shape[0] or row_scale.requires_grad:
         raise ValueError(f"row_scale: expected an fp32 [{x.shape[0]}] tensor without gradient, got {tuple(row_scale.shape)} "
@@ -549,25 +555,71 @@ def _row_scale_arg(x, row_scale):
     return _c(row_scale)
 
 
-def _drop_path_tail(a, M, K, weight, bias, out, D, x, row_scale):
-    """out = x + c * (a W^T + bias) on the bf16 and plain fp32 paths: the product into the fp32 ``out``, then the per-sample add."""
-    ops.linear_fwd(a, M, K, weight, bias, out, D, epi=EPI_NONE)
-    ops.drop_path_add(x, out, row_scale)
+# The frame both fused blocks share: out = x + c * last(f(LN(x))), ``last`` being the block's closing Linear.  A block function states f and
+# its gradient, once per arithmetic: split-operand (``ctx.x6``: fp32, bf16x3, bf16x3h with every product of the block on the bf16x6 / x3
+# kernels; activations travel as their bf16 pieces [M, nseg * cols]) or plain (bf16, fp32 without ``x6_block_ok``; activations in ``ctx.adt``).
+def _block_open(ctx, x, g, b, prec, row_scale, *widths):
+    """Everything up to and including the LayerNorm forward -> (x contiguous, LN(x) as the operand the arithmetic reads -- ``adt``
+    or pieces --, mean, rstd).  ``widths``: the block's feature widths besides D, for the ``x6_block_ok`` decision."""
+    ctx.adt = adt = ops.act_dtype(prec)
+    ctx.row_scale = row_scale
+    B, T, D = x.shape
+    M = B * T
+    x = _c(x)
+    ctx.up_bias = _chain_take(x)
+    ctx.x6 = adt == torch.float32 and ops.x6_block_ok(M, D, *widths)
+    if ctx.x6 and D <= 1024:
+        y, mean, rstd = ops.layernorm_fwd_split(x, D, M, D, g, b)       # LayerNorm writes the pieces itself (no fp32 y, no split pass)
+    else:
+        y, mean, rstd = ops.layernorm_fwd(x, D, M, D, g, b, adt)
+        if ctx.x6:
+            y = ops.split_ex(y, M, D)
+    return x, y, mean, rstd
 
 
-def _side_or_none(ctx, dout, M, D, kind):
-    """``_take_side`` for a plain block; a drop-path block must not read the side (it is unscaled) and clears it."""
-    if ctx.row_scale is None:
-        return _take_side(dout, M, D, kind)
-    _side.clear()
-    return None, None
+def _block_close(ctx, a, weight, bias, x):
+    """The closing product and the forward link: out = x + a W^T + bias in the GEMM's residual epilogue, or for a drop-path block
+    the product without the residual and out = x + c * (a W^T + bias) by ``ops.drop_path_add``.  ``a``: [M, K] in ``adt``, or its pieces."""
+    B, T, D = x.shape
+    M, c = B * T, ctx.row_scale
+    out = torch.empty_like(x)
+    if ctx.x6:
+        ops.nt_x6(a, weight, "fwd", M, out.view(M, D), bias=bias, residual=x.view(M, D) if c is None else None)
+    elif c is None:
+        ops.linear_fwd(a, M, weight.shape[1], weight, bias, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
+    else:
+        ops.linear_fwd(a, M, weight.shape[1], weight, bias, out, D, epi=EPI_NONE)
+    if c is not None:
+        ops.drop_path_add(x, out, c)
+    _chain_set(out, bias if c is None else None)
+    return out
 
 
-def _branch_grad(ctx, dout, dtype):
-    """The gradient entering the branch, in ``dtype``: dout itself, or c * dout for a drop-path block."""
-    if ctx.row_scale is None:
-        return ops.cast(dout, dtype)
-    return ops.row_scale(dout, ctx.row_scale, dtype)
+def _block_grad_in(ctx, dout, bias):
+    """The gradient entering the closing Linear (dout, or c * dout for a drop-path block) as the operand the arithmetic reads, and
+    that Linear's bias gradient -> (d, dbias).  Split-operand: the pieces, dbias always filled.  Plain: [M, D] in ``adt``; dbias is
+    the column sums the producing LayerNorm backward published with the bf16 copy, or None: ``linear_dw`` computes it then."""
+    B, T, D = dout.shape
+    M, c = B * T, ctx.row_scale
+    # first what the producing LayerNorm backward published for dout: plain fp32 has no side, and a drop-path block must not read it
+    # (it is unscaled) and clears it
+    if ctx.x6 or ctx.adt == torch.bfloat16:
+        if c is None:
+            d, dbias = _take_side(dout, M, D, ("split", ops.current_segments()) if ctx.x6 else "bf16")
+            if d is not None:
+                return d, dbias
+        else:
+            _side.clear()
+    # else computed here; split-operand: one pass leaves the split and the bias gradient
+    dbias = ops.grad_out(bias, (D,), dout.device) if ctx.x6 else None
+    d = (ops.cast(dout, ctx.adt) if c is None else ops.row_scale(dout, c, ctx.adt)).view(M, D)
+    return (ops.split_ex(d, M, D, colsum_out=dbias) if ctx.x6 else d), dbias
+
+
+def _block_ln_bwd(ctx, dy, dout, x, g, b, mean, rstd):
+    """The backward tail: LayerNorm backward of dy plus the residual gradient dout -> (dx, dgamma, dbeta), with the hand-off."""
+    M, D = dy.shape
+    return _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, ctx.adt, ctx.up_bias)
 
 
 class _DropPath(Function):
@@ -598,69 +650,45 @@ class _AttnBlock(Function):
     @staticmethod
     @_fwd
     def forward(ctx, x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec, row_scale=None):
-        adt = ops.act_dtype(prec)
-        ctx.row_scale = row_scale
         B, T, D = x.shape
         M = B * T
-        x = _c(x)
-        ctx.up_bias = _chain_take(x)
         inner3 = wqkv.shape[0]
         inner = inner3 // 3
-        ctx.x6 = adt == torch.float32 and ops.x6_block_ok(M, D, inner3, inner)
-        if not (ctx.x6 and D <= 1024):
-            y, mean, rstd = ops.layernorm_fwd(x, D, M, D, g, b, adt)
+        dh = inner // heads
+        x, y, mean, rstd = _block_open(ctx, x, g, b, prec, row_scale, inner3, inner)
+        adt, o6 = ctx.adt, None
         if ctx.x6:
-            # fp32 mode, every Linear product on the bf16x6 path: the block keeps the SPLITS of LN(x) and of the attention
-            # output (what the forward and the dW products both read), not the tensors themselves
-            dh = inner // heads
-            # LayerNorm writes the pieces itself (no fp32 y, no split pass)
-            y6, mean, rstd = ops.layernorm_fwd_split(x, D, M, D, g, b) if D <= 1024 else (ops.split_ex(y, M, D), mean, rstd)
+            # every Linear product on the bf16x6 / x3 path: the block keeps the SPLITS of LN(x) and of the attention output (what the
+            # forward and the dW products both read), not the tensors themselves
             ctx.path = path = ops.attention_path(adt, T, dh, need_grad=any(ctx.needs_input_grad), half_ok=True)
             # precision "bf16x3h": the fused attention kernels on half operands (2^-12 per rounding, fp32 sums, softmax and outputs);
             # q / k / v leave the to_qkv product as half (one rounding of the fp32 accumulator + bias, no fp32 tensor, no cast pass)
             qkv = torch.empty(B, T, inner3, dtype=torch.float16 if path == ops.ATTN_F16 else adt, device=x.device)
-            ops.nt_x6(y6, wqkv, "fwd", M, qkv.view(M, inner3), bias=bqkv)
+            ops.nt_x6(y, wqkv, "fwd", M, qkv.view(M, inner3), bias=bqkv)
             o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
             o6 = ops.split_ex(o.view(M, inner), M, inner)
-            out = torch.empty_like(x)
-            if row_scale is None:
-                ops.nt_x6(o6, wo, "fwd", M, out.view(M, D), bias=bo, residual=x.view(M, D))
+        else:
+            qkv = torch.empty(B, T, inner3, dtype=adt, device=x.device)
+            ops.linear_fwd(y, M, D, wqkv, bqkv, qkv, inner3)
+            # half_ok stays off: q/k/v and dO are in ``adt`` here, so of ops.ATTN_COLSUM_PATHS only the two bf16 ones can come back
+            ctx.path = path = ops.attention_path(adt, T, dh, need_grad=any(ctx.needs_input_grad))
+            assert path != ops.ATTN_F16
+            if path == ops.ATTN_PROBS:              # materialised fp32 probabilities (shapes the fused kernels lack)
+                o, saved = ops.attention_forward(path, ops.cast(qkv, torch.float32), B, T, heads, dh, scale)
+                o = ops.cast(o, adt)
             else:
-                ops.nt_x6(o6, wo, "fwd", M, out.view(M, D), bias=bo, residual=None)
-                ops.drop_path_add(x, out, row_scale)
-            # the fused backward needs the attention output itself (delta = rowsum(dO * O)), not only its split
-            ctx.save_for_backward(x, g, mean, rstd, y6, qkv, None if path == ops.ATTN_PROBS else o, o6, saved, wqkv, wo)
-            ctx.cfg = (heads, scale)
-            ctx.small = (b, bqkv, bo)
-            _chain_set(out, bo if row_scale is None else None)
-            return out
-        qkv = torch.empty(B, T, inner3, dtype=adt, device=x.device)
-        ops.linear_fwd(y, M, D, wqkv, bqkv, qkv, inner3)
-        dh = inner // heads
-        # half_ok stays off: q/k/v and dO are in ``adt`` here, so of ops.ATTN_COLSUM_PATHS only the two bf16 ones can come back
-        ctx.path = path = ops.attention_path(adt, T, dh, need_grad=any(ctx.needs_input_grad))
-        assert path != ops.ATTN_F16
-        if path == ops.ATTN_PROBS:              # materialised fp32 probabilities (shapes the fused kernels lack)
-            o, saved = ops.attention_forward(path, ops.cast(qkv, torch.float32), B, T, heads, dh, scale)
-            o = ops.cast(o, adt)
-        else:
-            o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
-        out = torch.empty_like(x)
-        if row_scale is None:
-            ops.linear_fwd(o.view(M, inner), M, inner, wo, bo, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
-        else:
-            _drop_path_tail(o.view(M, inner), M, inner, wo, bo, out, D, x, row_scale)
-        ctx.save_for_backward(x, g, mean, rstd, y, qkv, o, None, saved, wqkv, wo)
+                o, saved = ops.attention_forward(path, qkv, B, T, heads, dh, scale)
+        out = _block_close(ctx, o6 if ctx.x6 else o.view(M, inner), wo, bo, x)
+        # y: LN(x) in ``adt``, or its pieces; o6: the pieces of o (split-operand only; the fused backward needs o too: delta = rowsum(dO * O));
+        # ``saved``: what ops.attention_forward returned on ctx.path: the log-sum-exp, the probabilities, or None (nothing runs backward then)
+        ctx.save_for_backward(x, g, mean, rstd, y, qkv, None if ctx.x6 and path == ops.ATTN_PROBS else o, o6, saved, wqkv, wo)
         ctx.cfg = (heads, scale)
         ctx.small = (b, bqkv, bo)
-        _chain_set(out, bo if row_scale is None else None)
         return out
 
     @staticmethod
     @_scoped
     def backward(ctx, dout):
-        # y and o6 are bf16 pieces [M, nseg * cols] in the split-operand branch (o6 exists only there); ``saved`` is what
-        # ops.attention_forward returned on ctx.path: the log-sum-exp, the probabilities, or None (nothing runs backward then)
         x, g, mean, rstd, y, qkv, o, o6, saved, wqkv, wo = ctx.saved_tensors
         heads, scale = ctx.cfg
         B, T, D = x.shape
@@ -669,15 +697,13 @@ class _AttnBlock(Function):
         inner = inner3 // 3
         dh = inner // heads
         b, bqkv, bo = ctx.small
+        adt = ctx.adt
         dout = _c(dout)
+        d, dbo = _block_grad_in(ctx, dout, bo)                    # dY of the projection
         if ctx.x6:
-            d6, dbo = _side_or_none(ctx, dout, M, D, ("split", ops.current_segments()))   # the producing LayerNorm backward left both
-            if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
-                dbo = ops.grad_out(bo, (D,), x.device)
-                d6 = ops.split_ex(_branch_grad(ctx, dout, torch.float32).view(M, D), M, D, colsum_out=dbo)      # one pass: the split and the bias gradient
-            dwo = ops.tn_x6(d6, o6, M, wo)
+            dwo = ops.tn_x6(d, o6, M, wo)
             do = torch.empty(B, T, inner, dtype=torch.float32, device=x.device)
-            ops.nt_x6(d6, wo, "dx", M, do.view(M, inner))
+            ops.nt_x6(d, wo, "dx", M, do.view(M, inner))
             dbqkv = ops.grad_out(bqkv, (inner3,), x.device)
             if ctx.path == ops.ATTN_F16:
                 # the kernel writes the pieces of dqkv and per-image column sums itself: no fp32 dqkv, no split pass
@@ -690,41 +716,35 @@ class _AttnBlock(Function):
             dwqkv = ops.tn_x6(dq6, y, M, wqkv)
             dy = torch.empty(M, D, dtype=torch.float32, device=x.device)
             ops.nt_x6(dq6, wqkv, "dx", M, dy)
-            dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, torch.float32, ctx.up_bias)
-            return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None, None
-        adt = y.dtype
-        d_act, dbo = _side_or_none(ctx, dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
-        if d_act is None:
-            d_act = _branch_grad(ctx, dout, adt).view(M, D)       # dY of the projection, activation dtype
-        # bf16: dW of to_out is computed below, with dW of to_qkv, in one grouped split-K launch (d_act and o stay alive)
-        pair = adt == torch.bfloat16
-        if not pair:
-            dwo, dbo2 = ops.linear_dw(d_act, o.view(M, inner), M, D, inner, want_bias=dbo is None, weight=wo, bias=bo)
-            dbo = dbo if dbo is not None else dbo2
-        do = torch.empty(B, T, inner, dtype=adt, device=x.device)
-        ops.linear_dx(d_act, M, D, wo, do, inner)
-        dbqkv = None
-        if ctx.path in ops.ATTN_COLSUM_PATHS:
-            # the kernel also leaves per-image column sums of dqkv: to_qkv's bias gradient without another pass over dqkv
-            part = torch.empty(B, inner3, dtype=torch.float32, device=x.device)
-            dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale, colsum=part)
-            dbqkv = ops.colsum(part, B, inner3, inner3, ops.grad_out(bqkv, (inner3,), x.device))
-        elif ctx.path == ops.ATTN_PROBS:
-            dqkv = ops.cast(ops.attention_backward(ctx.path, ops.cast(qkv, torch.float32), None, ops.cast(do, torch.float32), saved,
-                                                   B, T, heads, dh, scale), adt)
         else:
-            dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale)
-        if pair:
-            (dwo, dbo2), (dwqkv, dbq2) = ops.linear_dw_pair(M, (d_act, o.view(M, inner), D, inner, wo, bo, dbo is None),
-                                                            (dqkv.view(M, inner3), y, inner3, D, wqkv, bqkv, dbqkv is None))
-            dbo = dbo if dbo is not None else dbo2
-        else:
-            dwqkv, dbq2 = ops.linear_dw(dqkv.view(M, inner3), y, M, inner3, D, want_bias=dbqkv is None, weight=wqkv, bias=bqkv)
-        dbqkv = dbqkv if dbqkv is not None else dbq2
-        dy = torch.empty(M, D, dtype=adt, device=x.device)
-        ops.linear_dx(dqkv.view(M, inner3), M, inner3, wqkv, dy, D)
-        dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, adt, ctx.up_bias)   # + residual gradient
-        return dx, dg, db, dwqkv, dbqkv, dwo, dbo, None, None, None, None
+            # bf16: dW of to_out is computed below, with dW of to_qkv, in one grouped split-K launch (d and o stay alive)
+            pair = adt == torch.bfloat16
+            if not pair:
+                dwo, dbo2 = ops.linear_dw(d, o.view(M, inner), M, D, inner, want_bias=dbo is None, weight=wo, bias=bo)
+                dbo = dbo if dbo is not None else dbo2
+            do = torch.empty(B, T, inner, dtype=adt, device=x.device)
+            ops.linear_dx(d, M, D, wo, do, inner)
+            dbqkv = None
+            if ctx.path in ops.ATTN_COLSUM_PATHS:
+                # the kernel also leaves per-image column sums of dqkv: to_qkv's bias gradient without another pass over dqkv
+                part = torch.empty(B, inner3, dtype=torch.float32, device=x.device)
+                dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale, colsum=part)
+                dbqkv = ops.colsum(part, B, inner3, inner3, ops.grad_out(bqkv, (inner3,), x.device))
+            elif ctx.path == ops.ATTN_PROBS:
+                dqkv = ops.cast(ops.attention_backward(ctx.path, ops.cast(qkv, torch.float32), None, ops.cast(do, torch.float32), saved,
+                                                       B, T, heads, dh, scale), adt)
+            else:
+                dqkv = ops.attention_backward(ctx.path, qkv, o, do, saved, B, T, heads, dh, scale)
+            if pair:
+                (dwo, dbo2), (dwqkv, dbq2) = ops.linear_dw_pair(M, (d, o.view(M, inner), D, inner, wo, bo, dbo is None),
+                                                                (dqkv.view(M, inner3), y, inner3, D, wqkv, bqkv, dbqkv is None))
+                dbo = dbo if dbo is not None else dbo2
+            else:
+                dwqkv, dbq2 = ops.linear_dw(dqkv.view(M, inner3), y, M, inner3, D, want_bias=dbqkv is None, weight=wqkv, bias=bqkv)
+            dbqkv = dbqkv if dbqkv is not None else dbq2
+            dy = torch.empty(M, D, dtype=adt, device=x.device)
+            ops.linear_dx(dqkv.view(M, inner3), M, inner3, wqkv, dy, D)
+        return (*_block_ln_bwd(ctx, dy, dout, x, g, b, mean, rstd), dwqkv, dbqkv, dwo, dbo, None, None, None, None)
 
 
 def attn_block(x, g, b, wqkv, bqkv, wo, bo, heads, scale, prec, *, row_scale=None):
@@ -740,53 +760,34 @@ class _MlpBlock(Function):
     @staticmethod
     @_fwd
     def forward(ctx, x, g, b, w1, b1, w2, b2, prec, row_scale=None):
-        adt = ops.act_dtype(prec)
-        ctx.row_scale = row_scale
         B, T, D = x.shape
         M = B * T
         Hd = w1.shape[0]
-        x = _c(x)
-        ctx.up_bias = _chain_take(x)
-        ctx.x6 = adt == torch.float32 and ops.x6_block_ok(M, D, Hd)
-        if not (ctx.x6 and D <= 1024):
-            y, mean, rstd = ops.layernorm_fwd(x, D, M, D, g, b, adt)
+        x, y, mean, rstd = _block_open(ctx, x, g, b, prec, row_scale, Hd)
+        adt = ctx.adt
         if ctx.x6:
-            # fp32 mode on the bf16x6 path: keeps the splits of LN(x) and of gelu(h) plus the pre-activation h; the fp32
-            # activation gelu(h) is never stored (the split kernel applies the GELU on its way); LayerNorm writes its pieces itself
-            y6, mean, rstd = ops.layernorm_fwd_split(x, D, M, D, g, b) if D <= 1024 else (ops.split_ex(y, M, D), mean, rstd)
+            # keeps the splits of LN(x) and of gelu(h) plus the pre-activation h; the fp32 activation gelu(h) is never stored (the
+            # split kernel applies the GELU on its way)
             h = torch.empty(M, Hd, dtype=adt, device=x.device)
             if ops.nt_split_ok(M, Hd, D):
-                a6 = ops.nt_x6_gelu_split(y6, w1, M, h, bias=b1)     # one launch: h (fp32) and the pieces of gelu(h)
+                a = ops.nt_x6_gelu_split(y, w1, M, h, bias=b1)       # one launch: h (fp32) and the pieces of gelu(h)
             else:
-                ops.nt_x6(y6, w1, "fwd", M, h, bias=b1)
-                a6 = ops.split_ex(h, M, Hd, op=1)
-            out = torch.empty_like(x)
-            if row_scale is None:
-                ops.nt_x6(a6, w2, "fwd", M, out.view(M, D), bias=b2, residual=x.view(M, D))
-            else:
-                ops.nt_x6(a6, w2, "fwd", M, out.view(M, D), bias=b2, residual=None)
-                ops.drop_path_add(x, out, row_scale)
-            ctx.save_for_backward(x, g, mean, rstd, y6, h, a6, w1, w2)
-            ctx.small = (b, b1, b2)
-            _chain_set(out, b2 if row_scale is None else None)
-            return out
-        # bf16: the fc1 epilogue leaves gelu'(pre-activation) for the backward pass (one multiply there instead of another
-        # erf evaluation per element) -- as ONE BYTE per element (GELU_GRAD_BITS = 8: gelu' is confined to [-0.13, 1.13], a
-        # 0.005-step code whose grid holds 0 and 1 exactly costs 0.24 % of its rms value and takes a quarter of the bytes out of fc1's store-bound epilogue
-        # and of fc2-dX's); fp32 exact mode keeps the pre-activation itself
-        g8 = adt == torch.bfloat16 and GELU_GRAD_BITS == 8 and Hd % 8 == 0
-        h = torch.empty(M, Hd, dtype=torch.uint8 if g8 else adt, device=x.device)
-        a = torch.empty(M, Hd, dtype=adt, device=x.device)
-        ops.linear_fwd(y, M, D, w1, b1, a, Hd, epi=(EPI_GELU_GRAD8 if g8 else EPI_GELU_GRAD) if adt == torch.bfloat16 else EPI_GELU,
-                       out2=h, ld_out2=Hd)
-        out = torch.empty_like(x)
-        if row_scale is None:
-            ops.linear_fwd(a, M, Hd, w2, b2, out, D, epi=EPI_RESIDUAL, aux=x, ld_aux=D)
+                ops.nt_x6(y, w1, "fwd", M, h, bias=b1)
+                a = ops.split_ex(h, M, Hd, op=1)
         else:
-            _drop_path_tail(a, M, Hd, w2, b2, out, D, x, row_scale)
+            # bf16: the fc1 epilogue leaves gelu'(pre-activation) for the backward pass (one multiply there instead of another
+            # erf evaluation per element) -- as ONE BYTE per element (GELU_GRAD_BITS = 8: gelu' is confined to [-0.13, 1.13], a
+            # 0.005-step code whose grid holds 0 and 1 exactly costs 0.24 % of its rms value and takes a quarter of the bytes out of fc1's store-bound epilogue
+            # and of fc2-dX's); fp32 exact mode keeps the pre-activation itself
+            g8 = adt == torch.bfloat16 and GELU_GRAD_BITS == 8 and Hd % 8 == 0
+            h = torch.empty(M, Hd, dtype=torch.uint8 if g8 else adt, device=x.device)
+            a = torch.empty(M, Hd, dtype=adt, device=x.device)
+            ops.linear_fwd(y, M, D, w1, b1, a, Hd, epi=(EPI_GELU_GRAD8 if g8 else EPI_GELU_GRAD) if adt == torch.bfloat16 else EPI_GELU,
+                           out2=h, ld_out2=Hd)
+        out = _block_close(ctx, a, w2, b2, x)
+        # y: LN(x), a: gelu(fc1) -- in ``adt``, or their pieces; h: fc1's pre-activation, or gelu' of it in the bf16 arithmetic
         ctx.save_for_backward(x, g, mean, rstd, y, h, a, w1, w2)
         ctx.small = (b, b1, b2)
-        _chain_set(out, b2 if row_scale is None else None)
         return out
 
     @staticmethod
@@ -796,50 +797,39 @@ class _MlpBlock(Function):
         B, T, D = x.shape
         M = B * T
         Hd = w1.shape[0]
+        b, b1, b2 = ctx.small
+        adt = ctx.adt
+        dout = _c(dout)
+        d, db2 = _block_grad_in(ctx, dout, b2)                       # dY of fc2
         if ctx.x6:
-            y6, a6 = y, a
-            dout = _c(dout)
-            b, b1, b2 = ctx.small
-            d6, db2 = _side_or_none(ctx, dout, M, D, ("split", ops.current_segments()))
-            if d6 is None or d6.dtype != torch.bfloat16 or d6.shape[1] != ops.current_segments() * D:
-                db2 = ops.grad_out(b2, (D,), x.device)
-                d6 = ops.split_ex(_branch_grad(ctx, dout, torch.float32).view(M, D), M, D, colsum_out=db2)
-            dw2 = ops.tn_x6(d6, a6, M, w2)
+            dw2 = ops.tn_x6(d, a, M, w2)
             db1 = ops.grad_out(b1, (Hd,), x.device)
             if ops.nt_split_ok(M, Hd, D):
-                dh6 = ops.nt_x6_dgelu_split(d6, w2, M, h, db1)   # one launch: the pieces of (dY W2) * gelu'(h) and its column sums
+                dh6 = ops.nt_x6_dgelu_split(d, w2, M, h, db1)    # one launch: the pieces of (dY W2) * gelu'(h) and its column sums
             else:
                 dh = torch.empty(M, Hd, dtype=torch.float32, device=x.device)
-                ops.nt_x6(d6, w2, "dx", M, dh)
+                ops.nt_x6(d, w2, "dx", M, dh)
                 dh6 = ops.split_ex(dh, M, Hd, op=2, h=h, colsum_out=db1)     # (dY W2) * gelu'(h), its split and its column sums
-            dw1 = ops.tn_x6(dh6, y6, M, w1)
+            dw1 = ops.tn_x6(dh6, y, M, w1)
             dy = torch.empty(M, D, dtype=torch.float32, device=x.device)
             ops.nt_x6(dh6, w1, "dx", M, dy)
-            dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, torch.float32, ctx.up_bias)
-            return dx, dg, db, dw1, db1, dw2, db2, None, None
-        adt = y.dtype
-        dout = _c(dout)
-        d_act, db2 = _side_or_none(ctx, dout, M, D, "bf16") if adt == torch.bfloat16 else (None, None)
-        if d_act is None:
-            d_act = _branch_grad(ctx, dout, adt).view(M, D)
-        b, b1, b2 = ctx.small
-        dw2, db2b = ops.linear_dw(d_act, a, M, D, Hd, want_bias=db2 is None, weight=w2, bias=b2)
-        db2 = db2 if db2 is not None else db2b
-        dh = torch.empty(M, Hd, dtype=adt, device=x.device)
-        if adt == torch.bfloat16:
-            # (dY W2) * gelu'(h); the epilogue also leaves per-64-row column sums of dh = fc1's bias-gradient partials
-            part = torch.empty((M + 63) // 64, Hd, dtype=torch.float32, device=x.device)
-            ops.linear_dx(d_act, M, D, w2, dh, Hd, epi=EPI_MUL8 if h.dtype == torch.uint8 else EPI_MUL, aux=h, ld_aux=Hd,
-                          colsum_partial=part)                                                 # h = gelu' here
-            db1 = ops.colsum(part, part.shape[0], Hd, Hd, ops.grad_out(b1, (Hd,), x.device))
-            dw1, _ = ops.linear_dw(dh, y, M, Hd, D, want_bias=False, weight=w1)
         else:
-            ops.linear_dx(d_act, M, D, w2, dh, Hd, epi=EPI_DGELU, aux=h, ld_aux=Hd)
-            dw1, db1 = ops.linear_dw(dh, y, M, Hd, D, weight=w1, bias=b1)
-        dy = torch.empty(M, D, dtype=adt, device=x.device)
-        ops.linear_dx(dh, M, Hd, w1, dy, D)
-        dx, dg, db = _ln_bwd_with_side(dy, x, D, g, b, mean, rstd, dout, M, adt, ctx.up_bias)
-        return dx, dg, db, dw1, db1, dw2, db2, None, None
+            dw2, db2b = ops.linear_dw(d, a, M, D, Hd, want_bias=db2 is None, weight=w2, bias=b2)
+            db2 = db2 if db2 is not None else db2b
+            dh = torch.empty(M, Hd, dtype=adt, device=x.device)
+            if adt == torch.bfloat16:
+                # (dY W2) * gelu'(h); the epilogue also leaves per-64-row column sums of dh = fc1's bias-gradient partials
+                part = torch.empty((M + 63) // 64, Hd, dtype=torch.float32, device=x.device)
+                ops.linear_dx(d, M, D, w2, dh, Hd, epi=EPI_MUL8 if h.dtype == torch.uint8 else EPI_MUL, aux=h, ld_aux=Hd,
+                              colsum_partial=part)                                             # h = gelu' here
+                db1 = ops.colsum(part, part.shape[0], Hd, Hd, ops.grad_out(b1, (Hd,), x.device))
+                dw1, _ = ops.linear_dw(dh, y, M, Hd, D, want_bias=False, weight=w1)
+            else:
+                ops.linear_dx(d, M, D, w2, dh, Hd, epi=EPI_DGELU, aux=h, ld_aux=Hd)
+                dw1, db1 = ops.linear_dw(dh, y, M, Hd, D, weight=w1, bias=b1)
+            dy = torch.empty(M, D, dtype=adt, device=x.device)
+            ops.linear_dx(dh, M, Hd, w1, dy, D)
+        return (*_block_ln_bwd(ctx, dy, dout, x, g, b, mean, rstd), dw1, db1, dw2, db2, None, None)
 
 
 def mlp_block(x, g, b, w1, b1, w2, b2, prec, *, row_scale=None):

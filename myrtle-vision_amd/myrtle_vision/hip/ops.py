@@ -16,6 +16,7 @@ sequence up to 8 192 tokens: the whole-head kernels up to 288, the key-tiled one
 The exact-fp32 attention core of ``"fp32"`` and ``"bf16x3"`` (and of the converted int8 model) does the same: the whole-head
 f32-MFMA kernels up to 272 tokens, the key-tiled ones above, so no length materialises the [B, H, N, N] probabilities.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -32,6 +33,7 @@ __all__ = ["EPI_NONE", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGELU", "EPI_EMBED", "EP
            "EPI_SPLIT_DGELU", "EPI_SPLIT_GELU"]
 
 _DT = {torch.float32: MV_F32, torch.bfloat16: MV_BF16}
+_X6_OUT = {torch.float32: MV_F32, torch.float16: _l.MV_F16}       # what the split-operand NT products (_nt_x6) can write
 
 
 def act_dtype(prec: str):
@@ -125,6 +127,30 @@ _timer = None
 def set_kernel_timer(timer):
     global _timer
     _timer = timer
+
+
+class _Timed:
+    """One bracket of ``_timed``: the start event on entry, the record once the launches went through (none if one raised)."""
+    __slots__ = ("name", "flops", "shape", "start")
+
+    def __init__(self, name, flops, shape):
+        self.name, self.flops, self.shape = name, flops, shape
+
+    def __enter__(self):
+        self.start = _timer.begin()
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            _timer.end(self.name, self.start, self.flops, shape=self.shape)
+
+
+_untimed = contextlib.nullcontext()
+
+
+def _timed(name, flops, shape=None):
+    """``with _timed(name, flops, shape):`` around the launches of one product.  With a KernelTimer installed: one record under ``name``
+    and under ``shape`` (on the steps it samples), from an event before the first launch to one after the last; else nothing at all."""
+    return _untimed if _timer is None else _Timed(name, flops, shape)
 
 
 _workspaces = {}
@@ -597,12 +623,10 @@ def nt_x6_gelu_split(y6, weight, M, h, *, bias):
     N, Kc = weight.shape
     nseg = current_segments()
     a6 = _split_buffer(M, N, h.device)
-    t0 = _timer.begin() if _timer is not None else None
-    check(lib().mv_gemm_nt_bf16(_p(y6), nseg * Kc, _p(split_weight(weight, "fwd")), nseg * Kc, _p(a6), nseg * N, MV_BF16, M, N,
-                                nseg * Kc, _p(bias), EPI_SPLIT_GELU, None, 0, nseg, _p(h), N, _s()),
-          "gemm_nt_bf16(split gelu)", M=M, N=N, K=nseg * Kc)
-    if t0 is not None:
-        _timer.end(f"gemm_nt_bf16x{nseg}", t0, 2.0 * M * N * Kc, shape=f"fwd N{N} K{Kc} split-gelu")
+    with _timed(f"gemm_nt_bf16x{nseg}", 2.0 * M * N * Kc, f"fwd N{N} K{Kc} split-gelu"):
+        check(lib().mv_gemm_nt_bf16(_p(y6), nseg * Kc, _p(split_weight(weight, "fwd")), nseg * Kc, _p(a6), nseg * N, MV_BF16, M, N,
+                                    nseg * Kc, _p(bias), EPI_SPLIT_GELU, None, 0, nseg, _p(h), N, _s()),
+              "gemm_nt_bf16(split gelu)", M=M, N=N, K=nseg * Kc)
     return a6
 
 
@@ -613,12 +637,10 @@ def nt_x6_dgelu_split(d6, weight, M, h, colsum_out):
     nseg = current_segments()
     dh6 = _split_buffer(M, K, h.device)
     part = torch.empty((M + 63) // 64, K, dtype=torch.float32, device=h.device)
-    t0 = _timer.begin() if _timer is not None else None
-    check(lib().mv_gemm_nt_bf16(_p(d6), nseg * N, _p(split_weight(weight, "dx")), nseg * N, _p(dh6), nseg * K, MV_BF16, M, K,
-                                nseg * N, None, EPI_SPLIT_DGELU, _p(h), K, nseg, _p(part), K, _s()),
-          "gemm_nt_bf16(split dgelu)", M=M, N=K, K=nseg * N)
-    if t0 is not None:
-        _timer.end(f"gemm_nt_bf16x{nseg}", t0, 2.0 * M * N * K, shape=f"dx N{K} K{N} split-dgelu")
+    with _timed(f"gemm_nt_bf16x{nseg}", 2.0 * M * N * K, f"dx N{K} K{N} split-dgelu"):
+        check(lib().mv_gemm_nt_bf16(_p(d6), nseg * N, _p(split_weight(weight, "dx")), nseg * N, _p(dh6), nseg * K, MV_BF16, M, K,
+                                    nseg * N, None, EPI_SPLIT_DGELU, _p(h), K, nseg, _p(part), K, _s()),
+              "gemm_nt_bf16(split dgelu)", M=M, N=K, K=nseg * N)
     colsum(part, part.shape[0], K, K, colsum_out)
     return dh6
 
@@ -635,11 +657,9 @@ def _tn_segments(dy6, x6, dw, M, N, K):
     nseg = current_segments()
     Mp = pad32(M)                                  # the splits' storage is zero-padded to whole stages (_split_buffer)
     ws = workspace(lib().mv_gemm_tn_workspace_bytes(N, K, nseg * Mp), dy6.device)
-    t0 = _timer.begin() if _timer is not None else None
     fn = lib().mv_gemm_tn_bf16_x6 if nseg == 6 else lib().mv_gemm_tn_bf16_x3
-    check(fn(_p(dy6), _p(x6), _p(dw), K, N, K, Mp, _p(ws), ws.numel(), _s()), f"gemm_tn_bf16_x{nseg}", M=N, N=K, rows=Mp)
-    if t0 is not None:
-        _timer.end(f"gemm_tn_bf16x{nseg}", t0, 2.0 * M * N * K, shape=f"dw N{N} K{K}")
+    with _timed(f"gemm_tn_bf16x{nseg}", 2.0 * M * N * K, f"dw N{N} K{K}"):
+        check(fn(_p(dy6), _p(x6), _p(dw), K, N, K, Mp, _p(ws), ws.numel(), _s()), f"gemm_tn_bf16_x{nseg}", M=N, N=K, rows=Mp)
 
 
 def _x6_ksplits(M, N):
@@ -651,26 +671,26 @@ def _x6_ksplits(M, N):
 
 
 def _nt_x6(a6, b6, out, ldc, M, N, Kc, bias, epi, aux=None, ld_aux=0, aux_i=0, tag="fwd"):
+    c_dt = _X6_OUT.get(out.dtype)
+    if c_dt is None:
+        raise ValueError(f"_nt_x6: the output is fp32 or IEEE half, got {out.dtype}")
+    if out.dtype == torch.float16 and epi != EPI_NONE:           # half output: q / k / v of precision "bf16x3h"
+        raise ValueError(f"_nt_x6: a half output takes no epilogue (EPI_NONE), got epi {epi}")
     nseg = current_segments()
     Kx = nseg * Kc
-    t0 = _timer.begin() if _timer is not None else None
     S = _x6_ksplits(M, N) if epi in (EPI_NONE, EPI_RESIDUAL) and ldc == N and (aux is None or ld_aux == N) else 1
     if S > 1 and (Kx % (128 * S) != 0 or out.dtype != torch.float32):
         S = 1
-    c_dt = MV_F32 if out.dtype == torch.float32 else _l.MV_F16       # half output: q / k / v of precision "bf16x3h" (EPI_NONE only)
-    if S > 1:
-        slabs = workspace(S * M * N * 4, out.device)
-        check(lib().mv_gemm_nt_bf16_ksplit(_p(a6), Kx, _p(b6), Kx, _p(slabs), M, N, Kx, S, _p(bias), _s()),
-              f"gemm_nt_bf16_ksplit(x{nseg})", M=M, N=N, K=Kx, S=S)
-        check(lib().mv_sum_slabs_add(_p(slabs), M * N, S, _p(aux) if epi == EPI_RESIDUAL else None, _p(out), M * N, _s()),
-              "sum_slabs_add", n=M * N)
-        if t0 is not None:
-            _timer.end(f"gemm_nt_bf16x{nseg}", t0, 2.0 * M * N * Kc, shape=f"{tag} N{N} K{Kc} epi{epi} S{S}")
-        return
-    check(lib().mv_gemm_nt_bf16(_p(a6), Kx, _p(b6), Kx, _p(out), ldc, c_dt, M, N, Kx, _p(bias), epi, _p(aux),
-                                ld_aux, aux_i, None, 0, _s()), f"gemm_nt_bf16(x{nseg})", M=M, N=N, K=Kx, epi=epi)
-    if t0 is not None:
-        _timer.end(f"gemm_nt_bf16x{nseg}", t0, 2.0 * M * N * Kc, shape=f"{tag} N{N} K{Kc} epi{epi}")
+    with _timed(f"gemm_nt_bf16x{nseg}", 2.0 * M * N * Kc, f"{tag} N{N} K{Kc} epi{epi}" + (f" S{S}" if S > 1 else "")):
+        if S > 1:
+            slabs = workspace(S * M * N * 4, out.device)
+            check(lib().mv_gemm_nt_bf16_ksplit(_p(a6), Kx, _p(b6), Kx, _p(slabs), M, N, Kx, S, _p(bias), _s()),
+                  f"gemm_nt_bf16_ksplit(x{nseg})", M=M, N=N, K=Kx, S=S)
+            check(lib().mv_sum_slabs_add(_p(slabs), M * N, S, _p(aux) if epi == EPI_RESIDUAL else None, _p(out), M * N, _s()),
+                  "sum_slabs_add", n=M * N)
+        else:
+            check(lib().mv_gemm_nt_bf16(_p(a6), Kx, _p(b6), Kx, _p(out), ldc, c_dt, M, N, Kx, _p(bias), epi, _p(aux),
+                                        ld_aux, aux_i, None, 0, _s()), f"gemm_nt_bf16(x{nseg})", M=M, N=N, K=Kx, epi=epi)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -684,12 +704,10 @@ def linear_fwd(x, M, K, weight, bias, out, ldc, *, lda=None, epi=EPI_NONE, aux=N
     lda = K if lda is None else lda
     if x.dtype == torch.bfloat16:
         pw = prepared_weight(weight)
-        t0 = _timer.begin() if _timer is not None else None
-        check(lib().mv_gemm_nt_bf16(_p(x), lda, _p(pw.w), pw.ldw, _p(out), ldc, _DT[out.dtype], M, N, K, _p(bias), epi,
-                                    _p(aux), ld_aux, aux_i, _p(out2), ld_out2, _s()),
-              "gemm_nt_bf16", M=M, N=N, K=K, epi=epi)
-        if t0 is not None:
-            _timer.end("gemm_nt_bf16", t0, 2.0 * M * N * K, shape=f"fwd N{N} K{K} epi{epi}")
+        with _timed("gemm_nt_bf16", 2.0 * M * N * K, f"fwd N{N} K{K} epi{epi}"):
+            check(lib().mv_gemm_nt_bf16(_p(x), lda, _p(pw.w), pw.ldw, _p(out), ldc, _DT[out.dtype], M, N, K, _p(bias), epi,
+                                        _p(aux), ld_aux, aux_i, _p(out2), ld_out2, _s()),
+                  "gemm_nt_bf16", M=M, N=N, K=K, epi=epi)
     elif (_x6_nt_ok(M, N, K) and out.dtype == torch.float32 and weight.dtype == torch.float32
           and (epi in (EPI_NONE, EPI_RESIDUAL, EPI_EMBED) and out2 is None
                or epi == EPI_GELU and ldc == N and (out2 is None or ld_out2 == N))):
@@ -716,12 +734,10 @@ def linear_dx(dy, M, N, weight, out, ldc, *, ld_dy=None, epi=EPI_NONE, aux=None,
     ld_dy = N if ld_dy is None else ld_dy
     if dy.dtype == torch.bfloat16:
         pw = prepared_weight(weight)
-        t0 = _timer.begin() if _timer is not None else None
-        check(lib().mv_gemm_nt_bf16(_p(dy), ld_dy, _p(pw.wt), pw.ldt, _p(out), ldc, _DT[out.dtype], M, K, N, None, epi,
-                                    _p(aux), ld_aux, 0, _p(colsum_partial), K if colsum_partial is not None else 0, _s()),
-              "gemm_nt_bf16(dx)", M=M, N=K, K=N, epi=epi)
-        if t0 is not None:
-            _timer.end("gemm_nt_bf16", t0, 2.0 * M * N * K, shape=f"dx N{K} K{N} epi{epi}")
+        with _timed("gemm_nt_bf16", 2.0 * M * N * K, f"dx N{K} K{N} epi{epi}"):
+            check(lib().mv_gemm_nt_bf16(_p(dy), ld_dy, _p(pw.wt), pw.ldt, _p(out), ldc, _DT[out.dtype], M, K, N, None, epi,
+                                        _p(aux), ld_aux, 0, _p(colsum_partial), K if colsum_partial is not None else 0, _s()),
+                  "gemm_nt_bf16(dx)", M=M, N=K, K=N, epi=epi)
     elif (_x6_nt_ok(M, K, N) and out.dtype == torch.float32 and weight.dtype == torch.float32
           and (epi == EPI_NONE or epi == EPI_DGELU and ldc == K and ld_aux == K)):
         _nt_x6(split_act(dy, M, N, ld_dy), split_weight(weight, "dx"), out, ldc, M, K, N, None, EPI_NONE, tag="dx")
@@ -749,11 +765,9 @@ def linear_dw(dy, x, M, N, K, *, ld_dy=None, ldx=None, want_bias=True, weight=No
     elif dy.dtype == torch.bfloat16:
         nbytes = lib().mv_gemm_tn_workspace_bytes(N, K, M)
         ws = workspace(nbytes, x.device)
-        t0 = _timer.begin() if _timer is not None else None
-        check(lib().mv_gemm_tn_bf16(_p(dy), ld_dy, _p(x), ldx, _p(dw), K, N, K, M, 0, _p(db), _p(ws), ws.numel(), _s()),
-              "gemm_tn_bf16", M=N, N=K, Kc=M)
-        if t0 is not None:
-            _timer.end("gemm_tn_bf16(+reduce+colsum)", t0, 2.0 * M * N * K, shape=f"dw N{N} K{K} bias{int(want_bias)}")
+        with _timed("gemm_tn_bf16(+reduce+colsum)", 2.0 * M * N * K, f"dw N{N} K{K} bias{int(want_bias)}"):
+            check(lib().mv_gemm_tn_bf16(_p(dy), ld_dy, _p(x), ldx, _p(dw), K, N, K, M, 0, _p(db), _p(ws), ws.numel(), _s()),
+                  "gemm_tn_bf16", M=N, N=K, Kc=M)
     elif _x6_tn_ok(M, N, K) and dy.dtype == torch.float32 and x.dtype == torch.float32:
         a6, b6 = split_act(dy, M, N, ld_dy, colsum_out=db if want_bias else None), split_act(x, M, K, ldx)
         _tn_segments(a6, b6, dw, M, N, K)
@@ -809,11 +823,9 @@ def _linear_dw_group(products):
         it.A, it.lda, it.B, it.ldb, it.C, it.ldc, it.M, it.N = _p(dy), ld_dy, _p(x), ldx, _p(dw), K, N, K
     addr = ctypes.addressof(items)
     ws = workspace(lib().mv_gemm_tn_group_workspace_bytes(addr, len(products), M), products[0][1].device)
-    t0 = _timer.begin() if _timer is not None else None
-    check(lib().mv_gemm_tn_bf16_group(addr, len(products), M, _p(ws), ws.numel(), _s()), "gemm_tn_bf16_group", Kc=M,
-          shapes=[(pr[3], pr[4]) for pr in products])
-    if t0 is not None:
-        _timer.end("gemm_tn_bf16_group(+reduce)", t0, 2.0 * M * sum(pr[3] * pr[4] for pr in products), shape=f"dw x{len(products)}")
+    with _timed("gemm_tn_bf16_group(+reduce)", 2.0 * M * sum(pr[3] * pr[4] for pr in products), f"dw x{len(products)}"):
+        check(lib().mv_gemm_tn_bf16_group(addr, len(products), M, _p(ws), ws.numel(), _s()), "gemm_tn_bf16_group", Kc=M,
+              shapes=[(pr[3], pr[4]) for pr in products])
     for dy, _x, _m, N, _K, ld_dy, _ldx, _dw, db in products:
         if db is not None:
             colsum(dy, M, N, ld_dy, db)
@@ -1344,12 +1356,10 @@ def linear_f16_supported(M, N, K):
 def linear_f16(x16, w16, M, N, K, bias, out, residual=None):
     """out fp32 [M, N] = x16 [M, K] . w16 [N, K]^T + bias (+ residual): half operands on v_mfma_f32_16x16x32_f16, fp32
     accumulation."""
-    t0 = _timer.begin() if _timer is not None else None
     epi, aux, ld_aux = (EPI_RESIDUAL, _p(residual), N) if residual is not None else (EPI_NONE, None, 0)
-    check(lib().mv_gemm_nt_f16(_p(x16), K, _p(w16), K, _p(out), N, M, N, K, _p(bias), epi, aux, ld_aux, None, 0, _s()),
-          "gemm_nt_f16", M=M, N=N, K=K)
-    if t0 is not None:
-        _timer.end("gemm_nt_f16", t0, 2.0 * M * N * K, shape=f"f16 N{N} K{K} epi{epi}")
+    with _timed("gemm_nt_f16", 2.0 * M * N * K, f"f16 N{N} K{K} epi{epi}"):
+        check(lib().mv_gemm_nt_f16(_p(x16), K, _p(w16), K, _p(out), N, M, N, K, _p(bias), epi, aux, ld_aux, None, 0, _s()),
+              "gemm_nt_f16", M=M, N=N, K=K)
     return out
 
 
@@ -1390,13 +1400,11 @@ def quant_affine_codes(x, rows, cols, scale, zero_point, qmin, qmax, pre_gelu=Fa
 def linear_codes(xc, wc, M, N, K, alpha, bias, out, residual=None):
     """out (fp32 or bf16) [M, N] = alpha * (xc [M, pad8(K)] . wc [N, pad8(K)]^T) + bias (+ residual fp32 [M, N]):
     integer-code operands on the bf16 MFMA path = exact int8 arithmetic (|codes| <= 256, fp32 accumulation)."""
-    t0 = _timer.begin() if _timer is not None else None
     epi, aux, ld_aux = (EPI_RESIDUAL, _p(residual), N) if residual is not None else (EPI_NONE, None, 0)
-    check(lib().mv_gemm_nt_bf16_scaled(_p(xc), xc.shape[1], _p(wc), wc.shape[1], _p(out), N, _DT[out.dtype], M, N, K,
-                                       float(alpha), _p(bias), epi, aux, ld_aux, 0, None, 0, _s()),
-          "gemm_nt_bf16_scaled", M=M, N=N, K=K)
-    if t0 is not None:
-        _timer.end("gemm_nt_bf16", t0, 2.0 * M * N * K)
+    with _timed("gemm_nt_bf16", 2.0 * M * N * K):
+        check(lib().mv_gemm_nt_bf16_scaled(_p(xc), xc.shape[1], _p(wc), wc.shape[1], _p(out), N, _DT[out.dtype], M, N, K,
+                                           float(alpha), _p(bias), epi, aux, ld_aux, 0, None, 0, _s()),
+              "gemm_nt_bf16_scaled", M=M, N=N, K=K)
     return out
 
 
@@ -1428,17 +1436,15 @@ def linear_i8(x8, w8, M, N, K, alpha, bias, icorr, out, residual=None, gelu_q8=N
     """out (fp32 or bf16) [M, N] = alpha * (x8 [M, pad16(K)] . w8 [N, pad16(K)]^T + icorr[N]) + bias (+ residual fp32):
     int8 operands on v_mfma_i32_16x16x64_i8, int32 accumulation.  ``gelu_q8 = (scale, zero_point)`` of the NEXT layer's
     quint8 quantiser: ``out`` is int8 [M, N] and receives that quantiser's codes (q - 128) of gelu(the product)."""
-    t0 = _timer.begin() if _timer is not None else None
     epi, aux, ld_aux = (EPI_RESIDUAL, _p(residual), N) if residual is not None else (EPI_NONE, None, 0)
     cdt, qs, qz = _DT.get(out.dtype), 0.0, 0
     if gelu_q8 is not None:
         if residual is not None or out.dtype != torch.int8:
             raise ValueError("gelu_q8 needs an int8 output and no residual")
         epi, cdt, qs, qz = _l.EPI_GELU_Q8, _l.MV_I8, float(gelu_q8[0]), int(gelu_q8[1])
-    check(lib().mv_gemm_nt_i8(_p(x8), x8.shape[1], _p(w8), w8.shape[1], _p(out), N, cdt, M, N, K, float(alpha),
-                              _p(bias), _p(icorr), epi, aux, ld_aux, qs, qz, _s()), "gemm_nt_i8", M=M, N=N, K=K, epi=epi)
-    if t0 is not None:
-        _timer.end("gemm_nt_i8", t0, 2.0 * M * N * K, shape=f"i8 N{N} K{K} epi{epi}")
+    with _timed("gemm_nt_i8", 2.0 * M * N * K, f"i8 N{N} K{K} epi{epi}"):
+        check(lib().mv_gemm_nt_i8(_p(x8), x8.shape[1], _p(w8), w8.shape[1], _p(out), N, cdt, M, N, K, float(alpha),
+                                  _p(bias), _p(icorr), epi, aux, ld_aux, qs, qz, _s()), "gemm_nt_i8", M=M, N=N, K=K, epi=epi)
     return out
 
 

@@ -415,6 +415,25 @@ def test_block_side_channel_hands_over_only_the_kind_the_consumer_reads():
     assert _taken_nothing(F._take_side(dx, M, D, ("split", 6)))
 
 
+@pytest.mark.parametrize("out_dtype,epi", [(torch.bfloat16, "EPI_NONE"), (torch.float16, "EPI_RESIDUAL")],
+                         ids=["bf16-out", "half-out-with-residual"])
+def test_nt_x6_refuses_an_output_it_cannot_write_before_the_library(monkeypatch, out_dtype, epi):
+    """The split-operand NT product writes fp32, or IEEE half without an epilogue (q / k / v of "bf16x3h").  A bf16 output used to
+    be written as half, and a half output with a residual failed inside the library: both are a ValueError at the call now, raised
+    before the library is loaded or called."""
+    from myrtle_vision.hip import ops
+
+    def reached(*a, **kw):
+        raise AssertionError("_nt_x6 reached the library")
+    monkeypatch.setattr(ops, "lib", reached)
+    M, N, Kc = 128, 64, 64
+    a6, b6 = torch.zeros(M, 6 * Kc, dtype=torch.bfloat16), torch.zeros(N, 6 * Kc, dtype=torch.bfloat16)
+    out = torch.zeros(M, N, dtype=out_dtype)
+    aux = torch.zeros(M, N) if epi == "EPI_RESIDUAL" else None
+    with pytest.raises(ValueError):
+        ops._nt_x6(a6, b6, out, N, M, N, Kc, None, getattr(ops, epi), aux, N if aux is not None else 0)
+
+
 def test_get_models_reads_reference_config_schema(tmp_path):
     from myrtle_vision.utils.models import get_models
     cfg = json.load(open(os.path.join(ROOT, "classification", "train_configs", "vit_tiny.json")))
