@@ -746,6 +746,33 @@ int mv_drop_path_add(const float* x, float* f, const float* c, int B, long per_s
 int mv_row_scale(const void* in, int in_code, void* out, int out_code, const float* c, int B, long per_sample,
                  mv_stream_t stream);
 
+/* ---- Random Erasing (csrc/random_erase.hip): a restatement of timm's RandomErasing (timm.data.random_erasing, _erase) on the
+ * project's Philox stream.  The reference has no call site: it never erases.  Same distribution as timm, different stream.
+ * mv_random_erase_draw, ONE launch of one workgroup: reads state = device uint64[2] (seed, step), writes boxes = int32
+ *   [B, max_count, 4] = (top, left, h, w) per erase (all four zero where nothing is erased) and used = device uint64[2], its own
+ *   array: the (seed, step) of THIS draw, which the fill reads; then, after a barrier, stores step + 1 to state[1].  So the next
+ *   call (or the next replay of a captured call) draws anew with no host value involved.  Per sample, in fp64: erased iff its
+ *   sample word < thr (thr = (uint64)(probability * 2^32), so 2^32 erases every sample); count = min_count + umulhi(word,
+ *   max_count - min_count + 1); per erase up to 10 attempts of  target = (min_area + u (max_area - min_area)) * H * W / count,
+ *   ratio = exp(log_lo + u' (log_hi - log_lo)), h = rint(sqrt(target * ratio)), w = rint(sqrt(target / ratio)), accepted iff
+ *   h < H and w < W, then top = umulhi(word, H - h + 1), left = umulhi(word, W - w + 1).  A box of zero extent is accepted and
+ *   erases nothing; ten failures leave the slot empty.  The counter of every word: the header comment of random_erase.hip.
+ *   area_ratio is a HOST array of four doubles (min_area, max_area, log_lo, log_hi), read before the launch: the C ABI passes no
+ *   floating-point argument wider than float by value.
+ *   MV_ERR_SHAPE: B < 0, H or W <= 0; MV_ERR_UNSUPPORTED: not 1 <= min_count <= max_count <= 8, thr > 2^32, not
+ *   0 < min_area <= max_area <= 1, or not log_lo <= log_hi, both finite; MV_ERR_ALIGN: a null area_ratio, a null or not 16-byte aligned device array.
+ *   B == 0 (with valid counts and thr) launches nothing, leaves state alone and looks at no pointer: MV_OK.
+ * mv_random_erase_apply: fills x = dense [B, Ch, H, W] of `elem` (MV_F32 | MV_BF16) IN PLACE from boxes; write-only, x is never
+ *   loaded.  mode 0 `const`: +0.0; mode 1 `rand`: one N(0,1) value per (sample, box, channel); mode 2 `pixel`: one N(0,1) value
+ *   per element, a function of (used, flat element index) only.  Normals: Box-Muller in fp32.  Where boxes of one sample overlap,
+ *   the LATER box wins (timm writes them in order) and no element is written twice; boxes are clipped to the image.  An empty
+ *   slot costs one 16-byte read.  MV_ERR_SHAPE: B < 0 or a dimension <= 0; MV_ERR_UNSUPPORTED: another elem or mode, max_count
+ *   outside 1..8, B*Ch*H*W >= 2^58 or B * max_count >= 2^31; MV_ERR_ALIGN: a null array or boxes not 16-byte aligned.  B == 0: MV_OK. */
+int mv_random_erase_draw(uint64_t* state, int32_t* boxes, uint64_t* used, int B, int H, int W, uint64_t thr,
+                         const double* area_ratio, int min_count, int max_count, mv_stream_t stream);
+int mv_random_erase_apply(void* x, int elem, const int32_t* boxes, const uint64_t* used, int B, int Ch, int H, int W, int max_count,
+                          int mode, mv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

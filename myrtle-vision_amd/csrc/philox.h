@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ONE definition for every kernel that draws
-// (dropout_kernel of elementwise.hip, drop_path_draw_kernel of drop_path.hip), so their streams agree with oracle/dropout_oracle.py
+// (dropout_kernel of elementwise.hip, drop_path_draw_kernel of drop_path.hip, the kernels of random_erase.hip), so their streams agree with oracle/dropout_oracle.py
 // word for word.  Counter (c0, c1, c2, c3), key (k0, k1) -> four 32-bit words.
 #pragma once
 #include <hip/hip_runtime.h>

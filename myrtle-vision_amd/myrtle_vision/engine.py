@@ -265,7 +265,26 @@ def _train_criterion(task, train_config):
     return SoftTargetCrossEntropy(smoothing, return_argmax=True), mixer
 
 
-_SEG_LOSS_KEYS = ("class_weights", "label_smoothing", "dice_weight", "dice_smooth")
+_ERASE_KEYS = ("reprob", "remode", "recount")
+
+
+def _random_eraser(task, train_config):
+    """-> ``RandomErasing`` or None from the optional ``train_config`` keys ``reprob`` (default 0), ``remode`` ("pixel" default,
+    "rand" or "const") and ``recount`` (default 1, timm's ``min_count``), timm's names: an extension, the reference never erases.
+    With ``reprob`` absent or 0 there is no eraser and ``utils.random_erasing`` is not even imported.  Classification only (masks
+    and boxes of the other tasks would have to follow): any of the keys on another task is an error."""
+    present = [k for k in _ERASE_KEYS if k in train_config]
+    if present and task != "classification":
+        raise ValueError(f"train_config key {present[0]!r} is a classification recipe (Random Erasing); task={task!r} does not "
+                         "take it")
+    if float(train_config.get("reprob", 0.0)) == 0.0:
+        return None
+    from myrtle_vision.utils.random_erasing import RandomErasing
+    return RandomErasing(probability=float(train_config["reprob"]), mode=train_config.get("remode", "pixel"),
+                         min_count=train_config.get("recount", 1))
+
+
+_SEG_LOSS_KEYS = ("class_weights","label_smoothing", "dice_weight", "dice_smooth")
 
 
 def _seg_loss_spec(task, train_config, num_classes=None):
@@ -459,10 +478,12 @@ def train_worker(rank, num_gpus, config, task="classification"):
     if task == "detection":
         _seg_loss_spec(task, config["train_config"])           # the segmentation recipe key on this task: an error before any work
         _check_distiller_config(config, task)
+        _random_eraser(task, config["train_config"])
         return _train_detection(rank, num_gpus, config)
     train_config = config["train_config"]
     data_config = parse_config(config["data_config_path"])
     train_criterion, mixer = _train_criterion(task, train_config)      # first: a recipe key on the wrong task fails before any work
+    eraser = _random_eraser(task, train_config)
     _check_distiller_config(config, task)
     seg_spec = _seg_loss_spec(task, train_config, data_config["number_of_classes"])
     device, world, batch_size, n_batch_accum, out_dir = _begin(rank, num_gpus, train_config, config["dist_config"])
@@ -511,7 +532,9 @@ def train_worker(rank, num_gpus, config, task="classification"):
                                 filepath=f"{out_dir}/vit_{iteration:06}", model_ema=_ema_state(optimizer, vit), distiller=distiller)
             if iteration % train_config["iters_per_val"] == 0 and window.at_start and rank == 0:
                 last_val, last_val_ema = _validate_twice(optimizer, validate)    # the EMA's figures are logged beside the plain ones
-            if distiller is not None:                            # DeiT distillation; the teacher sees the mixed batch, as in DeiT
+            if eraser is not None:                               # classification only; DeiT's order: erase per image, then mix
+                imgs = eraser(imgs)                              # in place, two launches; the teacher sees the erased batch too
+            if distiller is not None:                           # DeiT distillation; the teacher sees the mixed batch, as in DeiT
                 lam = 1.0
                 if mixer is not None:
                     imgs, lam = mixer(imgs, labels)

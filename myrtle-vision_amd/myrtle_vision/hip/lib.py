@@ -135,6 +135,8 @@ SIGNATURES = {
     "mv_drop_path_draw": ("pppp" "ii" "p", _I),
     "mv_drop_path_add": ("ppp" "il" "p", _I),
     "mv_row_scale": ("pipip" "il" "p", _I),
+    "mv_random_erase_draw": ("ppp" "iii" "Q" "p" "ii" "p", _I),
+    "mv_random_erase_apply": ("pipp" "iiii" "ii" "p", _I),
 }
 
 _lock = threading.Lock()

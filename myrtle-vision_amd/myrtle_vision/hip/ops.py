@@ -2043,3 +2043,50 @@ def row_scale(x, c, out_dtype=None, out=None):
         raise ValueError("row_scale: out is a contiguous tensor of x's shape, distinct from x")
     check(lib().mv_row_scale(_p(x), _DT[x.dtype], _p(out), _DT[out_dtype], _p(c), B, per, _s()), "row_scale", B=B, per_sample=per)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Random Erasing (timm's RandomErasing restated): boxes drawn and filled on the device
+# ------------------------------------------------------------------------------------------------------------
+RANDOM_ERASE_MODES = {"const": 0, "rand": 1, "pixel": 2}
+RANDOM_ERASE_MAX_COUNT = 8            # erases per sample (csrc/random_erase.hip)
+RANDOM_ERASE_WAVES = 4                # per workgroup of mv_random_erase_apply: one (channel, box row) each per pass
+RANDOM_ERASE_ROWS_PER_BLOCK = 32      # its grid has ceil(Ch * H / this) row bands per (sample, erase) slot ...
+RANDOM_ERASE_MAX_BANDS = 32           # ... and never more than this many: the Ch * h rows of a box go round bands * waves workers
+
+
+def random_erase_draw(state, B, H, W, *, thr, min_area, max_area, log_ratio, min_count, max_count):
+    """One launch (mv_random_erase_draw): fresh ``boxes`` int32 [B, max_count, 4] = (top, left, h, w), zeros where nothing is
+    erased, and ``used`` int64 [2] = the (seed, step) of this draw, from the Philox stream of ``state`` (device int64[2] = (seed,
+    step)); the kernel leaves step + 1 in ``state``.  thr = int(probability * 2**32); log_ratio = (log min_aspect, log max_aspect).
+    -> (boxes, used)"""
+    require_cuda(state)
+    boxes = torch.empty(B, max_count, 4, dtype=torch.int32, device=state.device)
+    used = torch.empty(2, dtype=torch.int64, device=state.device)
+    area_ratio = (ctypes.c_double * 4)(float(min_area), float(max_area), float(log_ratio[0]), float(log_ratio[1]))   # read by the call
+    check(lib().mv_random_erase_draw(_p(state), _p(boxes), _p(used), B, H, W, int(thr), ctypes.addressof(area_ratio), int(min_count),
+                                     int(max_count), _s()),
+          "random_erase_draw", B=B, H=H, W=W, thr=thr, min_area=min_area, max_area=max_area, log_ratio=tuple(log_ratio),
+          min_count=min_count, max_count=max_count)
+    return boxes, used
+
+
+def random_erase_apply(x, boxes, used, mode):
+    """Fill the boxes of a dense [B, Ch, H, W] fp32 / bf16 batch IN PLACE (mv_random_erase_apply; write-only): ``mode`` "const"
+    (+0.0), "rand" (one normal per sample, box and channel) or "pixel" (one normal per element).  boxes: int32 [B, max_count, 4]
+    and used: int64 [2], as ``random_erase_draw`` returns them.  -> x"""
+    require_cuda(x, boxes, used)
+    if mode not in RANDOM_ERASE_MODES:
+        raise ValueError(f"random_erase_apply: mode is one of {sorted(RANDOM_ERASE_MODES)}, got {mode!r}")
+    if x.dim() != 4 or not x.is_contiguous() or x.dtype not in _DT:
+        raise RuntimeError("random_erase_apply: a contiguous [B, Ch, H, W] fp32 or bf16 batch expected "
+                           f"(got {tuple(x.shape)}, {x.dtype}, contiguous={x.is_contiguous()})")
+    B, Ch, H, W = x.shape
+    if (boxes.dtype != torch.int32 or boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4 or not boxes.is_contiguous()
+            or used.dtype != torch.int64 or used.numel() != 2 or not used.is_contiguous()):
+        raise ValueError(f"random_erase_apply: boxes is a contiguous int32 [{B}, max_count, 4] and used a contiguous int64 [2], got "
+                         f"{tuple(boxes.shape)} {boxes.dtype} and {tuple(used.shape)} {used.dtype}")
+    check(lib().mv_random_erase_apply(_p(x), _DT[x.dtype], _p(boxes), _p(used), B, Ch, H, W, boxes.shape[1],
+                                      RANDOM_ERASE_MODES[mode], _s()),
+          "random_erase_apply", B=B, Ch=Ch, H=H, W=W, max_count=boxes.shape[1], mode=mode)
+    return x
