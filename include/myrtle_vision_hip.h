@@ -773,6 +773,31 @@ int mv_random_erase_draw(uint64_t* state, int32_t* boxes, uint64_t* used, int B,
 int mv_random_erase_apply(void* x, int elem, const int32_t* boxes, const uint64_t* used, int B, int Ch, int H, int W, int max_count,
                           int mode, mv_stream_t stream);
 
+/* ---- RandAugment (csrc/randaug.hip, arithmetic in csrc/randaug_math.h): an extension -- the reference augments with crop and flip
+ * only.  A restatement of timm's increasing op set (timm.data.auto_augment, `rand-m9-mstd0.5-inc1`), computed bit for bit as the
+ * Pillow 12 calls of datasets/transforms.RandAugment compute it.  One SLOT of the whole batch per pair of calls: src / dst uint8
+ * [B, H, W, 3]; ops int32 [B, num_ops] with ops[b, slot] = 0 (skipped: a copy) or 1..15 = AutoContrast, Equalize, Invert, Rotate,
+ * Posterize, Solarize, SolarizeAdd, Color, Contrast, Brightness, Sharpness, ShearX, ShearY, TranslateX, TranslateY; par fp64
+ * [B, num_ops, 8]: geometric ops (Rotate is an affine like the others, its matrix built by the host as Image.rotate builds it)
+ * par[0..5] = the coefficients of Image.transform(AFFINE) and par[6] = 0 bilinear / 1 bicubic; enhance ops par[0] = the factor
+ * (converted to float, as Image.blend does); Posterize / Solarize / SolarizeAdd par[0] = bits / threshold / addend.
+ * mv_randaug_stats, one workgroup per sample: for AutoContrast and Equalize the 3 x 256 lookup table into tables uint8
+ *   [B, 3, 256] (histograms by integer LDS atomics, table finished in the same launch; ImageOps.autocontrast in fp64, uncontracted;
+ *   ImageOps.equalize in 64-bit integers), for Contrast mean[b] = (int)(sum of L / (H * W) + 0.5) with L = (19595 R + 38470 G +
+ *   7471 B + 32768) >> 16.  A sample with any other op writes nothing.  No global atomic, no memset.
+ * mv_randaug_apply: writes every byte of dst (src != dst; Sharpness and the geometric ops read neighbours of src).  Geometric: per
+ *   output pixel xin = a0 (x + .5) + a1 (y + .5) + a2, yin likewise, fill colour where (xin, yin) is outside the image, else
+ *   Geometry.c's bilinear / bicubic filter in fp64.  Enhance: (uint8)(d + f (s - d)) in fp32, clipped when f is outside [0, 1], with
+ *   d = 0 (Brightness), L (Color), mean[b] (Contrast), ImageFilter.SMOOTH (Sharpness; border copied).  tables / mean are read
+ *   only by the samples whose op mv_randaug_stats serves.
+ * MV_ERR_SHAPE: B < 0 or > 65535, H or W <= 0, H * W * 3 >= 2^31, slot outside [0, num_ops); MV_ERR_UNSUPPORTED: a fill byte
+ * outside 0..255; MV_ERR_ALIGN: a null array, src == dst, par not 8-byte aligned.  B == 0: MV_OK, nothing launched. */
+int mv_randaug_stats(const uint8_t* src, const int32_t* ops, int num_ops, int slot, uint8_t* tables, int32_t* mean, int B, int H,
+                     int W, mv_stream_t stream);
+int mv_randaug_apply(const uint8_t* src, uint8_t* dst, const int32_t* ops, const double* par, int num_ops, int slot,
+                     const uint8_t* tables, const int32_t* mean, int fill0, int fill1, int fill2, int B, int H, int W,
+                     mv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,12 @@ resize + flip + ToTensor + Normalize for the whole batch, bit-exact to the Pillo
 segmentation training config) is two resamplings, each rounded to uint8 by Pillow: the GPU runs them as two kernels
 (``mv_image_resize_u8`` / ``mv_mask_resize_u8`` keep the intermediate uint8 image), with a second set of tables.
 
+With the optional ``"RandAugment"`` key (classification only; timm's increasing op set, ``datasets/transforms.RandAugment``) the
+chain is ... -> [RandomHorizontalFlip] -> RandAugment -> ToTensor -> [Normalize]: the worker also draws each slot's op and argument
+(``ra_op`` / ``ra_par``) and folds the flip into the last stage's horizontal tables; the GPU keeps the last resampling as uint8
+(``mv_image_resize_u8``), runs ``mv_randaug_stats`` + ``mv_randaug_apply`` per slot and finishes with ``mv_image_prepare`` through
+copying tables -- bit-exact to the Pillow calls of the host chain (tests/test_randaug_gpu.py).
+
 Detection (``DetectionDevicePlan``) differs in one way: every image leaves its chain with its own size and the batch is the
 zero-padded stack of them.  ``mv_image_prepare_ragged`` / ``mv_image_resize_u8_ragged`` take per-sample extents and write the
 padding and the padding mask themselves.
@@ -24,7 +30,7 @@ import random
 import numpy as np
 import torch
 
-from myrtle_vision.datasets.transforms import RandomResizedCrop
+from myrtle_vision.datasets.transforms import RANDAUG_GEOMETRIC, RANDAUG_OPS, RandAugment, RandomResizedCrop, affine_coefficients
 
 PRECISION_BITS = 22          # Pillow Resample.c: 32 - 8 - 2
 MAX_TAPS = 64                # mv_image_prepare's limit on taps per output pixel (downscale factor < ~31)
@@ -77,7 +83,8 @@ class DevicePlan:
     small CPU tensors (decoded frame + tables); ``collate`` stacks them; ``apply`` runs the kernels on the GPU."""
 
     def __init__(self, transform_config):
-        unknown = set(transform_config) - {"Resize", "RandomResizedCrop", "CenterCrop", "RandomHorizontalFlip", "Normalize"}
+        unknown = set(transform_config) - {"Resize", "RandomResizedCrop", "CenterCrop", "RandomHorizontalFlip", "Normalize",
+                                          "RandAugment"}
         if unknown:
             raise ValueError(f"transform chain not supported on the device path: {sorted(transform_config)}")
         self.resize = transform_config.get("Resize")
@@ -87,7 +94,14 @@ class DevicePlan:
         n = transform_config.get("Normalize")
         self.mean = tuple(float(v) for v in n["Mean"]) if n else (0.0, 0.0, 0.0)
         self.std = tuple(float(v) for v in n["Std"]) if n else (1.0, 1.0, 1.0)
+        # RandAugment (classification only): the host chain's own object makes the draws, so both sides draw alike; a bad
+        # value raises here, before any device work
+        self.randaug = RandAugment(transform_config["RandAugment"], n["Mean"] if n else None) if "RandAugment" in transform_config else None
         self._cache = {}
+        self._identity = {}
+
+    def __getstate__(self):
+        return dict(self.__dict__, _identity={})             # device tensors stay in the process that made them
 
     # ---- worker side ------------------------------------------------------------------------------------------
     def _tables(self, n_in, n_out):
@@ -128,12 +142,21 @@ class DevicePlan:
             t0, l0 = (oh - c) // 2, (ow - c) // 2
             bv, kv, yi, bh, kh, xi = bv[t0:t0 + c], kv[t0:t0 + c], yi[t0:t0 + c], bh[l0:l0 + c], kh[l0:l0 + c], xi[l0:l0 + c]
         flip = 1 if (self.flip and random.random() < 0.5) else 0
+        ra = None
+        if self.randaug is not None:
+            if mask is not None:
+                raise ValueError("RandAugment is for classification: geometric ops on a label map are not supported")
+            if flip:                                         # the flip precedes RandAugment: fold it into the final stage's
+                bh, kh, flip = bh[::-1], kh[::-1], 0         # horizontal tables (row order reversed, as TableFrame.transpose does)
+            ra = self.randaug_fields(self.randaug.draw(len(bh), len(bv)), len(bh), len(bv))
         s = {"raw": torch.from_numpy(a.copy()), "kh": torch.from_numpy(np.ascontiguousarray(kh)),
              "bh": torch.from_numpy(np.ascontiguousarray(bh)), "kv": torch.from_numpy(np.ascontiguousarray(kv)),
              "bv": torch.from_numpy(np.ascontiguousarray(bv)), "flip": flip}
         if first is not None:
             s.update(kv1=torch.from_numpy(np.ascontiguousarray(first[1])), bv1=torch.from_numpy(np.ascontiguousarray(first[0])),
                      kh1=torch.from_numpy(np.ascontiguousarray(first[4])), bh1=torch.from_numpy(np.ascontiguousarray(first[3])))
+        if ra is not None:
+            s.update(ra_op=torch.from_numpy(ra[0]), ra_par=torch.from_numpy(ra[1]))
         if mask is not None:
             m = np.asarray(mask, dtype=np.uint8)
             if m.shape != a.shape[:2]:
@@ -143,6 +166,25 @@ class DevicePlan:
             s.update(mask=torch.from_numpy(m.copy()), yi=torch.from_numpy(np.ascontiguousarray(yi)),
                      xi=torch.from_numpy(np.ascontiguousarray(xi)))
         return s
+
+    @staticmethod
+    def randaug_fields(slots, width, height):
+        """The slots ``RandAugment.draw`` returned -> (ra_op int32 [num_ops], ra_par float64 [num_ops, 8]) for ``mv_randaug_*``:
+        code 0 = skipped, else index in RANDAUG_OPS + 1; geometric ops carry the 6 affine coefficients (Rotate's matrix built as
+        ``Image.rotate`` builds it) + the filter (0 bilinear, 1 bicubic), the others their one argument."""
+        from PIL import Image
+        op, par = np.zeros(len(slots), np.int32), np.zeros((len(slots), 8), np.float64)
+        for i, slot in enumerate(slots):
+            if slot is None:
+                continue
+            name, arg, resample = slot
+            op[i] = RANDAUG_OPS.index(name) + 1
+            if name in RANDAUG_GEOMETRIC:
+                par[i, :6] = affine_coefficients(name, arg, width, height)
+                par[i, 6] = 1.0 if resample == Image.Resampling.BICUBIC else 0.0
+            elif arg is not None:
+                par[i, 0] = arg
+        return op, par
 
     # ---- collate (worker) -------------------------------------------------------------------------------------
     @staticmethod
@@ -183,6 +225,8 @@ class DevicePlan:
                "flip": torch.tensor([s["flip"] for s in samples], dtype=torch.uint8)}
         if has_mask:
             out.update(mask=mask, yi=torch.stack([s["yi"] for s in samples]), xi=torch.stack([s["xi"] for s in samples]))
+        if "ra_op" in samples[0]:                                            # RandAugment: [B, num_ops] codes, [B, num_ops, 8] arguments
+            out.update(ra_op=torch.stack([s["ra_op"] for s in samples]), ra_par=torch.stack([s["ra_par"] for s in samples]))
         if "kh1" in samples[0]:                                              # Resize -> RandomResizedCrop: stage-one tables
             k1 = max(max(s["kh1"].shape[1], s["kv1"].shape[1]) for s in samples)
             if k1 > MAX_TAPS:
@@ -208,11 +252,32 @@ class DevicePlan:
             raw = ops.image_resize_u8(raw, d["kh1"], d["bh1"], d["kv1"], d["bv1"])
             if mask is not None:
                 mask = ops.mask_resize_u8(mask, d["yi1"], d["xi1"])
+        if "ra_op" in d:
+            return self._apply_randaug(ops, raw, d), None
         imgs = ops.image_prepare(raw, d["kh"], d["bh"], d["kv"], d["bv"], d["flip"], self.mean, self.std)
         masks = None
         if mask is not None:
             masks = ops.mask_prepare(mask, d["yi"], d["xi"], d["flip"], mask_add)
         return imgs, masks
+
+    def _apply_randaug(self, ops, raw, d):
+        """The chain with RandAugment: the last resampling kept as uint8 (``mv_image_resize_u8``), ``num_ops`` slots of two launches
+        each, ping-ponging between two uint8 buffers, then ToTensor + Normalize by ``mv_image_prepare`` through copying tables."""
+        img = ops.image_resize_u8(raw, d["kh"], d["bh"], d["kv"], d["bv"])
+        B, oh, ow, _ = img.shape
+        other, tables, mean = torch.empty_like(img), None, None
+        for slot in range(d["ra_op"].shape[1]):
+            tables, mean = ops.randaug_stats(img, d["ra_op"], slot, tables, mean)
+            other = ops.randaug_apply(img, d["ra_op"], d["ra_par"], slot, tables, mean, self.randaug.fill, out=other)
+            img, other = other, img
+        key = (B, oh, ow, img.device)
+        ident = self._identity.get(key)
+        if ident is None:
+            self._identity.clear()
+            (bv, kv), (bh, kh) = (_identity_axis(np.arange(n)) for n in (oh, ow))
+            dev = lambda a: torch.from_numpy(a).to(img.device).unsqueeze(0).expand(B, -1, -1).contiguous()
+            ident = self._identity[key] = (dev(kh), dev(bh), dev(kv), dev(bv), torch.zeros(B, dtype=torch.uint8, device=img.device))
+        return ops.image_prepare(img, *ident, self.mean, self.std)
 
 
 # ---- detection: ragged batches ------------------------------------------------------------------------------------------

@@ -78,6 +78,148 @@ class RandomHorizontalFlip:
         return img, mask
 
 
+# ---- RandAugment: timm's increasing op set (timm.data.auto_augment, `rand-m9-mstd0.5-inc1`), restated -------------------------
+# An extension: the reference augments with crop and flip only.  The op set, the argument of every op and the position in the
+# chain are timm's; the order and source of the random draws are this project's own (python's ``random`` only, so that a worker
+# needs no numpy seeding).  Pillow calls only: this class is the reference that the device chain (device_transforms.DevicePlan
+# + csrc/randaug.hip) is held to, bit for bit.
+_BICUBIC = Image.Resampling.BICUBIC
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "PosterizeIncreasing", "SolarizeIncreasing", "SolarizeAdd",
+               "ColorIncreasing", "ContrastIncreasing", "BrightnessIncreasing", "SharpnessIncreasing", "ShearX", "ShearY",
+               "TranslateXRel", "TranslateYRel")                  # a slot's code is index + 1; 0 = the slot is skipped
+RANDAUG_DEFAULTS = {"magnitude": 9, "magnitude_std": 0.5, "num_ops": 2, "prob": 0.5, "interpolation": "bicubic"}
+RANDAUG_GEOMETRIC = frozenset(("Rotate", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel"))
+RANDAUG_ENHANCE = {"ColorIncreasing": "Color", "ContrastIncreasing": "Contrast", "BrightnessIncreasing": "Brightness",
+                   "SharpnessIncreasing": "Sharpness"}
+_RANDAUG_SIGNED = RANDAUG_GEOMETRIC | frozenset(RANDAUG_ENHANCE)
+
+
+def randaug_config(config):
+    """The ``"RandAugment"`` value of a ``transform_ops_*`` section -> the full parameter dict; ValueError naming what is wrong."""
+    config = {} if config is None else config
+    if not isinstance(config, dict):
+        raise ValueError(f"RandAugment: a dict of {sorted(RANDAUG_DEFAULTS)} expected, got {config!r}")
+    unknown = sorted(set(config) - set(RANDAUG_DEFAULTS))
+    if unknown:
+        raise ValueError(f"RandAugment: unknown key {unknown[0]!r} (known: {sorted(RANDAUG_DEFAULTS)})")
+    p = dict(RANDAUG_DEFAULTS, **config)
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+    if not number(p["magnitude"]) or not 0 <= p["magnitude"] <= 10:
+        raise ValueError(f"RandAugment: magnitude must be a number in [0, 10], got {p['magnitude']!r}")
+    if not number(p["magnitude_std"]) or not 0 <= p["magnitude_std"] < math.inf:
+        raise ValueError(f"RandAugment: magnitude_std must be a number >= 0, got {p['magnitude_std']!r}")
+    if not isinstance(p["num_ops"], int) or isinstance(p["num_ops"], bool) or p["num_ops"] < 1:
+        raise ValueError(f"RandAugment: num_ops must be an integer >= 1, got {p['num_ops']!r}")
+    if not number(p["prob"]) or not 0 <= p["prob"] <= 1:
+        raise ValueError(f"RandAugment: prob must be a number in [0, 1], got {p['prob']!r}")
+    if p["interpolation"] not in ("bilinear", "bicubic", "random"):
+        raise ValueError(f"RandAugment: interpolation must be 'bilinear', 'bicubic' or 'random', got {p['interpolation']!r}")
+    return p
+
+
+def randaug_argument(name, level, negate, width, height):
+    """The argument of op ``name`` at ``level`` in [0, 1] (timm's ``_*_level_to_arg``): degrees, shear factor, translation in pixels,
+    bits, threshold, addend, enhance factor; None for the three ops without one."""
+    sign = -1.0 if negate else 1.0
+    if name == "Rotate":
+        return sign * (30.0 * level)
+    if name in ("ShearX", "ShearY"):
+        return sign * (0.3 * level)
+    if name == "TranslateXRel":
+        return sign * (0.45 * level) * width
+    if name == "TranslateYRel":
+        return sign * (0.45 * level) * height
+    if name == "PosterizeIncreasing":
+        return 4 - int(4 * level)
+    if name == "SolarizeIncreasing":
+        return 256 - int(256 * level)
+    if name == "SolarizeAdd":
+        return min(128, int(110 * level))
+    if name in RANDAUG_ENHANCE:
+        return max(0.1, 1.0 + sign * (0.9 * level))
+    return None
+
+
+def rotate_matrix(degrees, width, height):
+    """The six AFFINE coefficients ``Image.rotate(degrees)`` hands to ``Image.transform`` (expand=False, centre of the image)."""
+    angle = -math.radians(degrees % 360.0)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    cx, cy = width / 2, height / 2
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
+def affine_coefficients(name, arg, width, height):
+    """Geometric op -> the coefficients of ``Image.transform(size, AFFINE, .)``."""
+    if name == "Rotate":
+        return rotate_matrix(arg, width, height)
+    return {"ShearX": (1, arg, 0, 0, 1, 0), "ShearY": (1, 0, 0, arg, 1, 0), "TranslateXRel": (1, 0, arg, 0, 1, 0),
+            "TranslateYRel": (1, 0, 0, 0, 1, arg)}[name]
+
+
+class RandAugment:
+    """``num_ops`` slots per image, each an op of ``RANDAUG_OPS`` drawn with replacement and applied with probability ``prob`` at a
+    magnitude drawn round ``magnitude`` (of 10).  ``fill``: the colour a geometric op leaves outside the source."""
+
+    def __init__(self, config=None, mean=None):
+        p = randaug_config(config)
+        self.magnitude, self.magnitude_std, self.num_ops = float(p["magnitude"]), float(p["magnitude_std"]), p["num_ops"]
+        self.prob, self.interpolation = float(p["prob"]), p["interpolation"]
+        self.fill = (128, 128, 128) if mean is None else tuple(min(255, round(255 * float(m))) for m in mean)
+        if len(self.fill) != 3 or min(self.fill) < 0:
+            raise ValueError(f"RandAugment: the fill colour comes from a 3-channel Normalize mean in [0, 1], got {mean!r}")
+        self.applied = None                               # the slots of the last call, as ``draw`` returned them
+
+    def draw(self, width, height):
+        """Every random draw of one image -> per slot None (skipped) or (name, argument, resample | None)."""
+        names = [RANDAUG_OPS[random.randrange(len(RANDAUG_OPS))] for _ in range(self.num_ops)]
+        slots = []
+        for name in names:
+            if random.random() > self.prob:
+                slots.append(None)
+                continue
+            m = random.gauss(self.magnitude, self.magnitude_std) if self.magnitude_std > 0 else self.magnitude
+            level = min(10.0, max(0.0, m)) / 10
+            negate = name in _RANDAUG_SIGNED and random.random() > 0.5
+            resample = None
+            if name in RANDAUG_GEOMETRIC:
+                resample = {"bilinear": _BILINEAR, "bicubic": _BICUBIC}.get(self.interpolation)
+                if resample is None:
+                    resample = random.choice((_BILINEAR, _BICUBIC))
+            slots.append((name, randaug_argument(name, level, negate, width, height), resample))
+        return slots
+
+    def apply_op(self, img, name, arg, resample):
+        from PIL import ImageEnhance, ImageOps
+        if name == "Rotate":
+            return img.rotate(arg, resample, fillcolor=self.fill)
+        if name in RANDAUG_GEOMETRIC:
+            coeffs = affine_coefficients(name, arg, *img.size)
+            return img.transform(img.size, Image.Transform.AFFINE, coeffs, resample, fillcolor=self.fill)
+        if name in RANDAUG_ENHANCE:
+            return getattr(ImageEnhance, RANDAUG_ENHANCE[name])(img).enhance(arg)
+        if name == "PosterizeIncreasing":
+            return ImageOps.posterize(img, arg)
+        if name == "SolarizeIncreasing":
+            return ImageOps.solarize(img, arg)
+        if name == "SolarizeAdd":
+            lut = [min(255, i + arg) if i < 128 else i for i in range(256)]
+            return img.point(lut * 3)
+        return {"AutoContrast": ImageOps.autocontrast, "Equalize": ImageOps.equalize, "Invert": ImageOps.invert}[name](img)
+
+    def __call__(self, img, mask=None):
+        if mask is not None:
+            raise ValueError("RandAugment is for classification: geometric ops on a label map are not supported")
+        img = img.convert("RGB")
+        self.applied = self.draw(*img.size)
+        for slot in self.applied:
+            if slot is not None:
+                img = self.apply_op(img, *slot)
+        return img, None
+
+
 class ToTensorNormalize:
     """ToTensor (HWC uint8 -> CHW float in [0,1]) followed by the optional Normalize(mean, std)."""
 
@@ -117,5 +259,7 @@ def build_transform(transform_config):
     if "RandomHorizontalFlip" in transform_config:
         ops.append(RandomHorizontalFlip())
     n = transform_config.get("Normalize")
+    if "RandAugment" in transform_config:                    # timm's position: after the geometry, before ToTensor
+        ops.append(RandAugment(transform_config["RandAugment"], n["Mean"] if n else None))
     ops.append(ToTensorNormalize(n["Mean"], n["Std"]) if n else ToTensorNormalize())
     return Compose(ops)

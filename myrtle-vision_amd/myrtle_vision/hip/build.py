@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MV_LIB_PATH") or os.path.join(LIB_DIR, "libmyrtle_vis
 INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 SOURCES = ["layernorm.hip", "gemm_bf16.hip", "gemm_f32.hip", "attention.hip", "attention_tiled.hip", "attention_f32.hip", "elementwise.hip", "seg_tail.hip",
            "detection.hip", "image_prep.hip", "pos_resize.hip", "mixup.hip", "seg_loss.hip", "optim_table.hip", "optim_family.hip", "drop_path.hip",
-           "distill.hip", "random_erase.hip"]
+           "distill.hip", "random_erase.hip", "randaug.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per file.  attention.hip, attention_tiled.hip (the whole-head and the key-tiled attention kernels): their softmax arithmetic sits between MFMAs, where a packed f32 operation (what SLP
 # vectorisation makes of adjacent scalar ones) costs more issue time than the two it replaces (MI355X_MICROARCH.md, vector-instruction

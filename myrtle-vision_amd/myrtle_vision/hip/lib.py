@@ -137,6 +137,8 @@ SIGNATURES = {
     "mv_row_scale": ("pipip" "il" "p", _I),
     "mv_random_erase_draw": ("ppp" "iii" "Q" "p" "ii" "p", _I),
     "mv_random_erase_apply": ("pipp" "iiii" "ii" "p", _I),
+    "mv_randaug_stats": ("pp" "ii" "pp" "iii" "p", _I),
+    "mv_randaug_apply": ("pppp" "ii" "pp" "iii" "iii" "p", _I),
 }
 
 _lock = threading.Lock()

@@ -2090,3 +2090,58 @@ def random_erase_apply(x, boxes, used, mode):
                                       RANDOM_ERASE_MODES[mode], _s()),
           "random_erase_apply", B=B, Ch=Ch, H=H, W=W, max_count=boxes.shape[1], mode=mode)
     return x
+
+
+# ------------------------------------------------------------------------------------------------------------
+# RandAugment (timm's increasing op set restated): the worker draws, these two launches per slot compute the pixels
+# ------------------------------------------------------------------------------------------------------------
+def _randaug_check(name, src, ra_op, slot, ra_par=None):
+    require_cuda(src, ra_op, ra_par)
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or not src.is_contiguous():
+        raise ValueError(f"{name}: a contiguous uint8 [B, H, W, 3] batch expected, got {tuple(src.shape)} {src.dtype}")
+    B = src.shape[0]
+    if ra_op.dtype != torch.int32 or ra_op.dim() != 2 or ra_op.shape[0] != B or not ra_op.is_contiguous():
+        raise ValueError(f"{name}: ra_op is a contiguous int32 [{B}, num_ops], got {tuple(ra_op.shape)} {ra_op.dtype}")
+    num_ops = ra_op.shape[1]
+    if not 0 <= slot < num_ops:
+        raise ValueError(f"{name}: slot {slot} outside [0, {num_ops})")
+    if ra_par is not None and (ra_par.dtype != torch.float64 or tuple(ra_par.shape) != (B, num_ops, 8) or not ra_par.is_contiguous()):
+        raise ValueError(f"{name}: ra_par is a contiguous float64 [{B}, {num_ops}, 8], got {tuple(ra_par.shape)} {ra_par.dtype}")
+    return B, src.shape[1], src.shape[2], num_ops
+
+
+def randaug_stats(src, ra_op, slot, tables=None, mean=None):
+    """One launch (mv_randaug_stats) for slot ``slot`` of a uint8 [B, H, W, 3] batch: the AutoContrast / Equalize lookup tables
+    (uint8 [B, 3, 256]) and the Contrast means (int32 [B]) of the samples whose op in this slot needs them; other samples' rows
+    are not written.  -> (tables, mean)"""
+    B, H, W, num_ops = _randaug_check("randaug_stats", src, ra_op, slot)
+    if tables is None:
+        tables = torch.empty(B, 3, 256, dtype=torch.uint8, device=src.device)
+    if mean is None:
+        mean = torch.empty(B, dtype=torch.int32, device=src.device)
+    if (tables.dtype != torch.uint8 or tuple(tables.shape) != (B, 3, 256) or not tables.is_contiguous() or mean.dtype != torch.int32
+            or tuple(mean.shape) != (B,) or not mean.is_contiguous()):
+        raise ValueError(f"randaug_stats: tables is a contiguous uint8 [{B}, 3, 256] and mean a contiguous int32 [{B}]")
+    require_cuda(tables, mean)
+    check(lib().mv_randaug_stats(_p(src), _p(ra_op), num_ops, slot, _p(tables), _p(mean), B, H, W, _s()),
+          "randaug_stats", B=B, H=H, W=W, num_ops=num_ops, slot=slot)
+    return tables, mean
+
+
+def randaug_apply(src, ra_op, ra_par, slot, tables, mean, fill=(128, 128, 128), out=None):
+    """One launch (mv_randaug_apply): slot ``slot`` of every sample, out of place.  ra_op int32 [B, num_ops] (0 = copy, 1..15 =
+    index + 1 in ``datasets.transforms.RANDAUG_OPS``), ra_par float64 [B, num_ops, 8], tables / mean from ``randaug_stats`` of the same slot and ``src``.
+    -> uint8 [B, H, W, 3], every byte written"""
+    B, H, W, num_ops = _randaug_check("randaug_apply", src, ra_op, slot, ra_par)
+    if out is None:
+        out = torch.empty_like(src)
+    if out.dtype != torch.uint8 or out.shape != src.shape or not out.is_contiguous() or out.data_ptr() == src.data_ptr():
+        raise ValueError("randaug_apply: out is a contiguous uint8 tensor of src's shape and not src itself")
+    if (tables.dtype != torch.uint8 or tuple(tables.shape) != (B, 3, 256) or not tables.is_contiguous() or mean.dtype != torch.int32
+            or tuple(mean.shape) != (B,) or not mean.is_contiguous()):
+        raise ValueError(f"randaug_apply: tables is a contiguous uint8 [{B}, 3, 256] and mean a contiguous int32 [{B}]")
+    require_cuda(tables, mean, out)
+    check(lib().mv_randaug_apply(_p(src), _p(out), _p(ra_op), _p(ra_par), num_ops, slot, _p(tables), _p(mean), int(fill[0]),
+                                 int(fill[1]), int(fill[2]), B, H, W, _s()),
+          "randaug_apply", B=B, H=H, W=W, num_ops=num_ops, slot=slot, fill=tuple(fill))
+    return out

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end throughput of the reference-style training LOOP (engine.train_worker: DataLoader workers decoding JPEGs,
 GPU image preparation, model step, per-iteration loss print) on a synthetic RESISC-45 tree -- what classification/train.py
-delivers, next to bench.py's resident-batch number.   usage: bench_train_loop.py [per_class=24] [batch=256] [epochs=4] [task=classification|segmentation]"""
+delivers, next to bench.py's resident-batch number.
+usage: bench_train_loop.py [per_class=24] [batch=256] [epochs=4] [task=classification|segmentation] [train config file name]"""
 import builtins, copy, json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "myrtle-vision_amd"))
@@ -13,8 +14,9 @@ from myrtle_vision.datasets.synthetic import make_dlrsd, make_resisc45
 from myrtle_vision.engine import train_worker
 
 tmp = tempfile.mkdtemp(prefix="mv_loop_")
-cfg = json.load(open(os.path.join(ROOT, task, "train_configs", "vit_base.json" if task == "classification" else "seg_base.json")))
-data = json.load(open(os.path.join(ROOT, task, "data_configs", "data_config.json")))
+name = sys.argv[5] if len(sys.argv) > 5 else ("vit_base.json" if task == "classification" else "seg_base.json")
+cfg = json.load(open(os.path.join(ROOT, task, "train_configs", name)))
+data = json.load(open(os.path.join(ROOT, task, cfg["data_config_path"])))         # every shipped config names data_configs/...
 t0 = time.time()
 if task == "classification":
     data["dataset_path"] = make_resisc45(os.path.join(tmp, "NWPU-RESISC45"), classes=45, per_class=per_class)
